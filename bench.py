@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """TD3 gradient-steps/s on MI355X (BASELINE.json metric), HalfCheetah-v4 shapes, batch 256/GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--runs R] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--config C]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,15 +13,21 @@ index draw + HBM gather from a 1e6-row replay ring pre-filled with synthetic tra
 (SURVEY.md §8d), the twin-critic update and, every policy_freq=2 steps, the actor update +
 Polyak.  N GPUs = data parallel: every rank owns a replay shard and samples its own 256
 rows; gradients are all-reduced over RCCL (xGMI) before Adam, so one step is one optimizer step
-on a global batch of 256·N rows.  ``value`` = optimizer steps/s (the median of ``--runs`` timed
-runs of K steps), ``samples_per_s`` = rows consumed per second over all ranks (weak scaling).
+on a global batch of 256·N rows.  ``value`` = optimizer steps/s over the K timed steps,
+``ms_per_step`` = the milliseconds one of them took, ``samples_per_s`` = rows consumed per second
+over all ranks (weak scaling).
 
-Prints ONE JSON line on rank 0 (the driver contract) with a ``roofline`` object for the
+A plain run sets up, takes the W warm-up steps, times the K steps (one timed region), writes the
+learner's state after the last timed step with ``--dump-outputs DIR`` (``dump_outputs``) and prints
+ONE JSON line on rank 0 (the driver contract).  Everything else is behind ``--full``: the timed
+region is repeated (``--runs``, 5 there unless given; ``value`` = the median run)
+and the line gains a ``roofline`` object for the
 dominant kernel (HIP-event timed live; ``step_frac`` = the step's algorithmic FLOP / measured
 step time / fp32 MFMA peak), a ``gather`` object for the replay-ring sample kernel (bytes / HIP
 event time vs the 8 TB/s HBM peak) and a ``cpu_baseline`` (the torch-CPU restatement of the
 reference step, oracle/td3_torch_cpu.py, on the host cores of this box: rank 0, N=1 only, in a
-child process).  Each rank pins its host thread to 8 CPUs of its GPU's NUMA node before touching
+child process); ``--no-roofline`` / ``--no-cpu-baseline`` leave those parts out of a ``--full``
+run.  Each rank pins its host thread to 8 CPUs of its GPU's NUMA node before touching
 the GPU (``pin_host_thread``; ``BENCH_PIN=0`` turns it off) and reports them in ``host_pin``.
 """
 from __future__ import annotations
@@ -394,24 +400,35 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs of this node, one rank each (default 1; under an external launcher "
                          "it must equal WORLD_SIZE)")
-    ap.add_argument("--steps", type=int, default=2000, help="steps per timed run")
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps (one timed region)")
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--runs", type=int, default=5,
-                    help="timed runs of --steps steps each; value = their median (SURVEY.md §8d)")
+    ap.add_argument("--runs", type=int, default=None,
+                    help="repeat the timed region of --steps steps; value = the median run "
+                         "(SURVEY.md §8d).  Default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: 5 timed runs, the "
+                         "per-stage roofline, the gather line and the torch-CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the learner's state (parameters, targets, Adam "
+                         "moments: what the last timed step left its caller) as DIR/<name>.npy")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="halfcheetah")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dp-self", action="store_true",
                     help="diagnostic: run the data-parallel stage lists (grad-only dW, RCCL all-reduce, "
                          "flat Adam) on a one-rank communicator, to price the DP path without peers")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the stage table, the roofline and the gather line")
     ap.add_argument("--launch", choices=["auto", "graph", "eager"], default="auto",
                     help="step launch mode: hipGraph replay, direct launches, or auto (replay while the "
                          "GPU has caught up with the host, direct launches while steps are queued)")
     ap.add_argument("--eager", action="store_true", help="same as --launch eager")
     ap.add_argument("--norm", choices=["layer", "none", "weight_normalization"], default="layer",
                     help="network normalisation (SURVEY §8d measures norm=layer; featured configs only)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.runs is None:
+        args.runs = 5 if args.full else 1
+    return args
 
 
 def _free_port():
@@ -582,9 +599,11 @@ def run_rank(args):
     if hold_gc:
         gc.enable()
     dt = float(np.median(runs))
+    if args.dump_outputs:              # before anything below takes further steps
+        dump_outputs(pol, args.dump_outputs, rank)
 
     rows, fam, roof, gat = None, None, None, None
-    if not args.no_roofline:           # every rank runs it: profiled steps contain collectives
+    if args.full and not args.no_roofline:           # every rank runs it: profiled steps contain collectives
         rows = stage_table(pol, rb, B, iters=50 if cfg["kind"] != "particles" else 3,
                            reps=5 if cfg["kind"] != "particles" else 1)
         gat = gather_line(pol, rb, cfg)
@@ -608,7 +627,7 @@ def run_rank(args):
     cpu = None
     if prev_cpus is not None:            # the CPU baseline gets every CPU the job may use
         os.sched_setaffinity(0, prev_cpus)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_child(args.config)
 
     if rank == 0:
@@ -618,12 +637,34 @@ def run_rank(args):
         dist.destroy_process_group()
 
 
+def dump_outputs(pol, path, rank=0):
+    """What the last timed step left its caller, as ``path/<name>.npy`` (float32, flat, in
+    ``state_dict()`` order): the four networks and the Adam moments of both optimizers, a few MB for
+    every config.  ``train`` returns nothing; this state is its result.  Every rank makes the calls
+    (a data-parallel optimizer ``state_dict()`` gathers its sharded moments), rank 0 writes.  The
+    run's inputs are fixed by its arguments (``torch.manual_seed(1000)``, the learner / ring / fill
+    seeds in ``run_rank``), so two builds given the same arguments can be compared array by array."""
+    def flat(arrays):
+        return np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in arrays])
+    out = {name: flat(getattr(pol, name).numpy_dict().values())
+           for name in ("actor", "critic", "actor_target", "critic_target")}
+    for name in ("actor", "critic"):
+        state = getattr(pol, name + "_optimizer").state_dict()["state"]
+        for key in ("exp_avg", "exp_avg_sq"):
+            out[f"{name}_adam_{key}"] = flat([state[i][key].numpy() for i in sorted(state)])
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(path, name + ".npy"), a)
+
+
 def result_line(args, cfg, world, dt, runs, roof=None, gat=None, rows=None, cpu=None, host_pin=None):
     """The driver's JSON line.  ``value`` = optimizer steps/s of the job: every rank takes the same
     step at once (the replicas all-reduce one global batch of B·world rows per step), so this is
     the TD3 gradient-step rate (TD3_featured.py:123-171: one ``train`` = one step) at the global
-    batch in ``config``; the rows consumed are ``samples_per_s``.  ``dt`` is the median of the timed
-    runs (the slowest rank's clock in each)."""
+    batch in ``config``; the rows consumed are ``samples_per_s``.  ``dt`` is the time of the timed
+    run of ``args.steps`` steps, the median one when the region was repeated (the slowest rank's
+    clock in each)."""
     B = cfg["batch"]
     steps_s = args.steps / dt
     metric = "TD3 gradient-steps/sec @ batch 256, HalfCheetah-v4, 1/2/4/8 GPU"
@@ -653,7 +694,8 @@ def result_line(args, cfg, world, dt, runs, roof=None, gat=None, rows=None, cpu=
         # (N-GPU lines stay comparable with the per-GPU "@ batch 256" label)
         "batch_gradients_per_s": round(steps_s * world, 3),
         "runs": [round(args.steps / r, 3) for r in runs],
-        "value_is": f"median of {len(runs)} timed runs of {args.steps} steps each; one step = one "
+        "value_is": (f"median of {len(runs)} timed runs of {args.steps} steps each" if len(runs) > 1
+                     else f"one timed run of {args.steps} steps") + "; one step = one "
                     f"optimizer step of every rank on a global batch of {B}x{world} rows",
     }
     if roof is not None:

@@ -98,3 +98,50 @@ def test_pin_host_thread_modes(monkeypatch):
     finally:
         os.sched_setaffinity(0, before)
     assert bench._parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
+
+
+def test_plain_run_times_the_steps_once_and_full_repeats_them():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (plain.full, plain.runs, plain.dump_outputs) == (False, 1, None)
+    assert bench.parse_args(["--full"]).runs == 5
+    assert bench.parse_args(["--runs", "3"]).runs == 3
+    line = bench.result_line(plain, bench.CONFIGS["halfcheetah"], 1, 0.002, [0.002])
+    assert line["steps"] == 20 and line["ms_per_step"] == pytest.approx(0.1)
+    assert line["value"] == pytest.approx(1e4) and line["runs"] == [line["value"]]
+    for k in ("roofline", "gather", "stage_us", "cpu_baseline"):
+        assert k not in line
+
+
+def test_dump_outputs_writes_float32_arrays_on_rank0_only(tmp_path):
+    """bench.dump_outputs on a stand-in learner: the four networks and the Adam moments, flat, in
+    state_dict order; every rank makes the calls, only rank 0 writes."""
+    import numpy as np
+    import torch
+
+    class View:
+        def __init__(self, base):
+            self.base = base
+
+        def numpy_dict(self):
+            return {"w": np.full((2, 3), self.base, np.float64), "b": np.arange(2, dtype=np.float32)}
+
+    class Opt:
+        def state_dict(self):
+            return {"state": {i: {"step": torch.tensor(1.0), "exp_avg": torch.full((2,), float(i)),
+                                  "exp_avg_sq": torch.full((3,), 10.0 + i)} for i in (1, 0)}}
+
+    class Pol:
+        actor, critic, actor_target, critic_target = View(1), View(2), View(3), View(4)
+        actor_optimizer = critic_optimizer = Opt()
+
+    bench.dump_outputs(Pol(), str(tmp_path / "r1"), rank=1)
+    assert not (tmp_path / "r1").exists()
+    bench.dump_outputs(Pol(), str(tmp_path / "r0"), rank=0)
+    names = ["actor", "critic", "actor_target", "critic_target", "actor_adam_exp_avg",
+             "actor_adam_exp_avg_sq", "critic_adam_exp_avg", "critic_adam_exp_avg_sq"]
+    assert sorted(os.listdir(tmp_path / "r0")) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(tmp_path / "r0" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 and a.ndim == 1 for a in got.values())
+    assert got["critic"].tolist() == [2.0] * 6 + [0.0, 1.0]
+    assert got["actor_adam_exp_avg"].tolist() == [0.0, 0.0, 1.0, 1.0]
+    assert got["critic_adam_exp_avg_sq"].tolist() == [10.0] * 3 + [11.0] * 3

@@ -45,7 +45,7 @@ def _worker(tmp_path, argv):
 
 @pytest.mark.parametrize("n", [2, 4])
 def test_launcher_starts_n_ranks_and_forwards_rank0_line(tmp_path, capfd, n):
-    argv = ["--gpus", str(n), "--steps", "20", "--warmup", "5"]
+    argv = ["--gpus", str(n), "--steps", "20", "--warmup", "5", "--full"]      # --full: 5 timed runs
     rc = bench.launch_workers(argv, n, worker=_worker(tmp_path, argv))
     assert rc == 0
     out = capfd.readouterr().out
