@@ -29,21 +29,17 @@ enum Pro : int {
                        // MFMA, ReLU, LayerNorm: the A rows of layer 1 (one launch for two layers)
   kProL0G = 5,         // kProL0 with the input rows sampled from the replay ring (as kProGather)
   kProHeadBwd = 6,     // the actor loss's Q1 head backward (dU3 = -1/B w4 on every row): dZ3 =
-                       // relu'(LN3_bwd(dU3)) with LN3's statistics from the H3 rows themselves;
-                       // ex[3] = w4, ex[4] = b4, ex[5] = Q1 out (n-tile 0), exf[0] = -1/B
+                       // relu'(LN3_bwd(dU3)) with LN3's statistics from the H3 rows themselves
+                       // (operands: head_bwd_pro)
 };
-// kProL0 / kProL0G operand slots: ex[8] = W0 [N0p][32], ex[9] = b0, ex[10] = H0 out (nullable,
-// ld exi[5]), exi[5] = N0p (<= 512, the layer-1 Kp), exi[6] = K0 (input width, <= 32),
-// kProL0G ring outputs: ex[3] (ld exi[8]) and ex[0] (ld exi[3]) = copies of the input row,
-// ex[1] / ex[2] = reward / not_done (record offset exi[1]); exi[0] = record offset of the input.
 constexpr int kL0XS = 36;        // LDS row stride of the staged layer-0 input rows
 
 // Row kernels (one batch row per wave) between the GEMM stages; they reuse GemmProb's
-// ex / exi / exf operand slots (layout documented at each row function in kernels.hip).
+// ex / exi / exf operand slots (one slot namespace per kind below).
 enum RowKind : int {
   kRowPolicyHead = 0,    // a' = clamp(ma*tanh(head(LN3(H3))) + clip(eps)) or pi = ma*tanh(...)
-  kRowCriticLoss = 1,    // min(Q1',Q2') target, mse grad, Q head and LN3 backward of Q_j
-  kRowActorLoss = 2,     // -mean Q1(s, pi(s)): head and LN3 backward of Q1
+  // 1 and 2 stay unused (retired kinds): the values are template arguments, i.e. part of the
+  // kernel names in profiles/ and of the Stage names
   kRowActorHeadBwd = 3,  // dQ1/da (Q1 LN1 bwd, W1 action cols), tanh bwd, actor head + LN3 bwd
   kRowCriticLossP = 4,   // TD3_particles: the same over A Q outputs, optional CDQ
   kRowActorLossP = 5,    // TD3_particles: -mean over B*A
@@ -55,6 +51,300 @@ enum RowKind : int {
   kRowTargetLoss = 8,    // target heads -> y (:140-142), g_j = 2/B (Q_j - y) (:148), squared errors
   kRowLnBwd = 9,         // dZ = relu'(LN_bwd(dU)) of full rows (layer 0, no GEMM follows)
 };
+
+// ------------------------------------------------------------------ operand slots
+// GemmProb::ex (pointers) / exi (ints) / exf (floats) by kind: every kind names its slots here, once
+// for the kernels (kernels.hip) and the host planner (td3.hip).  Per kind: pointer slots, integer
+// slots, float slots, each enum closed by its slot count.  "x3" / "x2" slots are consecutive, one
+// per network, indexed kName + n.
+constexpr int kMaxEx = 24;
+constexpr int kMaxExi = 12, kMaxExf = 4;
+#define TD3_SLOTS_FIT(kind)                                                                        \
+  static_assert(kind::kNumPtr <= kMaxEx && kind::kNumInt <= kMaxExi && kind::kNumFlt <= kMaxExf, \
+                #kind ": operand slots past GemmProb's arrays")
+
+// LayerNorm 3 + head: the leading slots of kRowPolicyHead, kRowActorLossP and kRowUnitLoss
+namespace ln3_head {
+enum : int {
+  kH3 = 0,       // last hidden rows (post-ReLU) [Bp][ld3]
+  kGamma3 = 1,   // LN3 affine
+  kBeta3 = 2,
+  kW4 = 3,       // head weight rows [nout][ldw4]
+  kB4 = 4,       // head bias
+  kNumPtr
+};
+enum : int {
+  kK3 = 0,       // real width of H3
+  kLd3 = 1,      // its row stride
+  kNumInt
+};
+}  // namespace ln3_head
+
+// kRowPolicyHead (row_policy_head)
+namespace policy_head {
+using namespace ln3_head;
+enum : int {
+  kNoise = ln3_head::kNumPtr,   // smoothing noise [Bp][ldn]: read (kGenNoise = 0) or written (drawn here)
+  kOut,          // out: critic input rows, the action at columns kActCol.. (ld kLdOut)
+  kTanh,         // out: tanh of the head [Bp][32]
+  kU3,           // out: LN3 output rows
+  kStats3,       // out: LN3 (mean, rstd) [2][Bp]
+  kOut2,         // out, nullable: second critic-input buffer for the action (ld kLdOut)
+  kNumPtr
+};
+enum : int {
+  kLdw4 = ln3_head::kNumInt,
+  kLdOut,
+  kGenNoise,     // 1: draw the noise (Philox), 0: read kNoise
+  kAd,           // action width
+  kActCol,       // first action column of the out rows
+  kLdNoise,
+  kTarget,       // 1: target smoothing; 0: policy
+  kClamp,        // clamp a' to +-max_action (TD3_featured :135-137; TD3_particles :179-181 has none)
+  kNumInt
+};
+enum : int {
+  kMaxAction = 0,   // 1 for TD3_particles: tanh output (:68)
+  kPolicyNoise,
+  kNoiseClip,
+  kNumFlt
+};
+}  // namespace policy_head
+TD3_SLOTS_FIT(policy_head);
+
+// kRowUnitLoss (row_unit_loss); Aout = unit dZ3_j
+namespace unit_loss {
+using namespace ln3_head;
+enum : int {
+  kQ = ln3_head::kNumPtr,   // out: Q_j [Bp]
+  kU3,           // out: LN3 output rows of Q_j
+  kStats3,       // out: LN3 (mean, rstd) [2][Bp]
+  kDU3,          // out: unit dU3_j rows (w4)
+  kNumPtr
+};
+enum : int { kNumInt = ln3_head::kNumInt, kNumFlt = 0 };
+}  // namespace unit_loss
+TD3_SLOTS_FIT(unit_loss);
+
+// kRowActorLossP (row_actor_loss_p); Aout = dZ3
+namespace actor_loss_p {
+using namespace ln3_head;
+enum : int {
+  kQ = ln3_head::kNumPtr,   // out: Q [Bp][32]
+  kNumPtr
+};
+enum : int {
+  kNq = ln3_head::kNumInt,   // Q outputs per row
+  kLdw4,
+  kNumInt
+};
+enum : int {
+  kGradScale = 0,   // -1/(B*nq)
+  kNumFlt
+};
+}  // namespace actor_loss_p
+TD3_SLOTS_FIT(actor_loss_p);
+
+// kProHeadBwd (pro_headbwd): H3, the LN3 affine and the widths are the GEMM's own A / lng / lnb /
+// Kreal / Kp; the head comes in the slots it has in ln3_head
+namespace head_bwd_pro {
+using ln3_head::kW4;
+using ln3_head::kB4;
+enum : int {
+  kQ = ln3_head::kNumPtr,   // out: Q1 [Bp] (n-tile 0)
+  kNumPtr
+};
+enum : int { kNumInt = 0 };
+enum : int {
+  kGradScale = 0,   // dL/dQ of a live row: -1/B
+  kNumFlt
+};
+}  // namespace head_bwd_pro
+TD3_SLOTS_FIT(head_bwd_pro);
+
+// Shared by kRowActorHeadBwd and kRowActorHeadBwdP: the actor's head / LN3 operands and outputs
+// (Aout = dZ3 of the actor); slots 0..4 / 0..2 are the kind's own
+namespace actor_bwd {
+enum : int {
+  kTanh = 5,     // tanh of the actor head [Bp][32]
+  kW4,           // actor head weight rows
+  kH3,           // actor H3 rows
+  kStats3,       // actor LN3 (mean, rstd)
+  kGamma3,       // actor LN3 gamma
+  kDZ4,          // out: dZ4 of the actor (ld 32)
+  kDU3,          // out: dU3 of the actor
+  kNumPtr
+};
+enum : int {
+  kActCol = 3,   // first action column of the Q1 input rows
+  kAd,           // action width
+  kK3,
+  kLd3,
+  kLdw4,
+  kNumInt
+};
+enum : int {
+  kMaxAction = 0,   // scale of the policy output
+  kNumFlt
+};
+}  // namespace actor_bwd
+
+// kRowActorHeadBwd (row_actor_head_bwd): dQ1/da through Q1's layer 0
+namespace actor_head_bwd {
+using namespace actor_bwd;
+enum : int {
+  kDU0 = 0,      // dU0 of Q1(s, pi)
+  kH0,           // H0 of Q1(s, pi)
+  kStats0,       // LN0 (mean, rstd) of Q1
+  kGamma0,       // LN0 gamma of Q1
+  kW1,           // layer-0 weight of Q1 [N0][ldw1]: the action columns are read
+  kW1T = actor_bwd::kNumPtr,   // nullable: those columns transposed [ad][kLdW1T] (ring_l0::kTCopy wrote them)
+  kNumPtr
+};
+enum : int {
+  kK0 = 0,       // real width of H0
+  kLd0,
+  kLdw1,
+  kLdW1T = actor_bwd::kNumInt,
+  kNumInt
+};
+}  // namespace actor_head_bwd
+TD3_SLOTS_FIT(actor_head_bwd);
+
+// kRowActorHeadBwdP (row_actor_head_bwd_p): dQ1/da through lnorm1 of the Q1 input
+namespace actor_head_bwd_p {
+using namespace actor_bwd;
+enum : int {
+  kDUin = 0,     // grad of the lnorm1 output of Q1(s, pi)
+  kXin,          // lnorm1 input rows
+  kStatsIn,      // lnorm1 (mean, rstd)
+  kGammaIn,      // lnorm1 gamma
+};
+enum : int {
+  kKin = 0,      // real input width
+  kLdIn,
+};
+}  // namespace actor_head_bwd_p
+TD3_SLOTS_FIT(actor_head_bwd_p);
+
+// kRowCriticLossP (row_critic_loss_p); x3 = (target q1, target q2 (= target q1 without CDQ), online q_j);
+// Aout = dZ3_j
+namespace critic_loss_p {
+enum : int {
+  kH3 = 0,       // x3
+  kGamma3 = 3,   // x3
+  kBeta3 = 6,    // x3
+  kW4 = 9,       // x3: [nq][ldw4]
+  kB4 = 12,      // x3
+  kReward = 15,
+  kNotDone,
+  kDZ4,          // out: dZ4_j (ld 32)
+  kDU3,          // out: dU3_j
+  kU3,           // out: LN3 output rows of Q_j
+  kStats3,       // out: LN3 (mean, rstd) of Q_j
+  kY,            // out: target [Bp][32] (written by j = 0)
+  kSqErr,        // out: squared errors of Q_j, summed over the outputs [Bp]
+  kQ,            // out: Q_j [Bp][32]
+  kNumPtr
+};
+enum : int {
+  kK3 = 0,
+  kLd3,
+  kJ,            // which online critic
+  kNq,           // Q outputs per row
+  kLdw4,
+  kCdq,          // clipped double-Q on
+  kNumInt
+};
+enum : int {
+  kDiscount = 0,
+  kGradScale,    // 2/(B*nq)
+  kNumFlt
+};
+}  // namespace critic_loss_p
+TD3_SLOTS_FIT(critic_loss_p);
+
+// kRowTargetLoss (row_target_loss); x2 = (q1, q2)
+namespace target_loss {
+enum : int {
+  kH3 = 0,       // x2: H3 of the target critics
+  kGamma3 = 2,   // x2
+  kBeta3 = 4,    // x2
+  kW4 = 6,       // x2
+  kB4 = 8,       // x2
+  kReward = 10,
+  kNotDone,
+  kQ,            // x2: online Q_j [Bp] (kRowUnitLoss wrote them)
+  kY = 14,       // out: target y [Bp]
+  kDZ4,          // x2, out: dZ4 of Q_j (ld 32)
+  kSqErr = 17,   // out: squared errors [2][Bp]
+  kG,            // x2, out: g_j = 2/B (Q_j - y) [Bp]
+  kNumPtr = 20
+};
+enum : int {
+  kK3 = 0,
+  kLd3,
+  kNumInt
+};
+enum : int {
+  kDiscount = 0,
+  kGradScale,    // 2/B
+  kNumFlt
+};
+}  // namespace target_loss
+TD3_SLOTS_FIT(target_loss);
+
+// kRowLnBwd (row_lnbwd)
+namespace ln_bwd {
+enum : int {
+  kDU = 0,       // dU rows
+  kH,            // post-ReLU activations
+  kStats,        // LN (mean, rstd) [2][Bp]
+  kGamma,
+  kDZ,           // out: dZ rows
+  kNumPtr
+};
+enum : int {
+  kLd = 0,       // row stride
+  kK,            // real width
+  kNumInt
+};
+enum : int { kNumFlt = 0 };
+}  // namespace ln_bwd
+TD3_SLOTS_FIT(ln_bwd);
+
+// The ring / layer-0 family: kProGather, kProL0, kProL0G (and the plain layer 0 that keeps a
+// transposed weight copy)
+namespace ring_l0 {
+enum : int {
+  // ring outputs, written by a problem's first column tile (each nullable)
+  kRowCopy2 = 0,  // second copy of the sampled input row (ld kLdRowCopy2)
+  kReward,        // reward / not_done of the sampled records [Bp]
+  kNotDone,
+  kRowCopy,       // kProL0G: first copy of the row (ld kLdRowCopy); kProGather stores it to Aout (ld ldao)
+  // layer 0 inside the layer-1 launch (kProL0 / kProL0G)
+  kW0 = 8,        // [N0p][32] (or its k-quad image, GemmProb::w0sk)
+  kB0,
+  kH0,            // out, nullable: H0 rows (ld kN0p)
+  // a stand-alone layer 0: row tile 0 also writes its weight rows' columns [kTCol, kTCol + kTN)
+  kTCopy = 12,    // nullable: transposed [kTN][Nout]
+  kNumPtr
+};
+enum : int {
+  kRecOff = 0,    // offset of the input row inside the record
+  kRecOffRw,      // offset of reward (not_done follows it)
+  kLdRowCopy2 = 3,
+  kN0p = 5,       // padded layer-0 width (<= 512, the layer-1 Kp)
+  kK0,            // input width (<= 32)
+  kLdRowCopy = 8,
+  kTCol = 10,
+  kTN,
+  kNumInt
+};
+enum : int { kNumFlt = 0 };
+}  // namespace ring_l0
+TD3_SLOTS_FIT(ring_l0);
+#undef TD3_SLOTS_FIT
 
 // Waves of a single-stage GEMM launch (gemm_kernel): input-grad stages (MODE 1) and 16-column
 // stages (WN = 0) run 16 waves — half the prologue rows per wave (their LN-backward / head
@@ -73,8 +363,6 @@ constexpr int gemm_nw(int mode, int wn, int pro) {
   return (TD3_GEMM_NW16 && wn != kWn4x2 && pro != kProL0 && pro != kProL0G && (mode == 1 || wn == 0)) ? 16
                                                                                                    : kGemmWaves;
 }
-
-constexpr int kMaxEx = 24;
 
 struct GemmProb {
   // The first 136 bytes (pointers, then ints, no implicit padding) are everything a GEMM
@@ -104,19 +392,19 @@ struct GemmProb {
   // (td3.hip Group::P4 / T4): ldw = 4, wsk = 4 * Np -- the 16 lanes of an MFMA fragment load (16 or 32
   // consecutive n, one k-quad) read 256 contiguous bytes instead of 16 rows' pieces.
   int wsk;
-  int w0sk;                       // kProL0*: the same for W0 (ex[8]): 0 = row-major [N0p][32]
+  int w0sk;                       // kProL0*: the same for W0 (ring_l0::kW0): 0 = row-major [N0p][32]
   int wpad_;
-  // head-prologue operands (meaning per kind: see the prologue functions in kernels.hip)
+  // operands of the row kinds and of the prologues with extra operands (slot names per kind above)
   float* ex[kMaxEx];
-  int exi[12];
-  float exf[4];
+  int exi[kMaxExi];
+  float exf[kMaxExf];
   uint64_t seed;
   const Counters* ctr;
 };
 
 // kProGather: the step's replay-ring sample.  Every workgroup draws the indices of its 32 rows
 // (Philox step = total_it + 1, exactly as gather_kernel) and reads its A rows from the records
-// (GemmProb::exi[0] = offset of the row inside the record, Kreal = its width).
+// (ring_l0::kRecOff = offset of the row inside the record, Kreal = its width).
 struct RingSide {
   const float* data; int rec;
   const int64_t* d_size;          // sample range [0, *d_size)

@@ -191,12 +191,12 @@ template <int RPW>
 __device__ __forceinline__ void pro_headbwd(const GemmProb& P, float* smem, const Ctx& c) {
   constexpr int RB = 2;
   float g[8], w[8], rm[8], bb[8];
-  rv_load(w, P.ex[3], P.Kp, c.lane);
+  rv_load(w, P.ex[head_bwd_pro::kW4], P.Kp, c.lane);
   if (P.norm) {
     rv_load(g, P.lng, P.Kp, c.lane);
     rv_load(bb, P.lnb, P.Kp, c.lane);
   }
-  const float b4 = gld(P.ex[4]);
+  const float b4 = gld(P.ex[head_bwd_pro::kB4]);
   real_mask(rm, P.Kreal, c.lane);
   const float invK = 1.0f / (float)P.Kreal;
   const bool t0 = c.nt == 0;
@@ -237,12 +237,12 @@ __device__ __forceinline__ void pro_headbwd(const GemmProb& P, float* smem, cons
         for (int j = 0; j < 8; ++j)
           x[r][j] = P.norm ? __fmaf_rn(__fmaf_rn(h[r][j], rstd[r], nb), g[j], bb[j]) : h[r][j];
         const float q = wsum(rv_pdot(x[r], w, P.Kreal, c.lane)) + b4;
-        if (c.lane == 0) gst(P.ex[5] + (c.m0 + c.wave * RPW + r0 + r), q);
+        if (c.lane == 0) gst(P.ex[head_bwd_pro::kQ] + (c.m0 + c.wave * RPW + r0 + r), q);
       }
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
-      const float gq = c.m0 + c.wave * RPW + r0 + r < P.B ? P.exf[0] : 0.f;
+      const float gq = c.m0 + c.wave * RPW + r0 + r < P.B ? P.exf[head_bwd_pro::kGradScale] : 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) gu[r][j] = gq * w[j];
     }
@@ -265,23 +265,25 @@ __device__ __forceinline__ void rv_load_u(float (&v)[8], const float* __restrict
   }
 }
 
-// A problem's first column tile also stores its rows for the later stages (no extra loads):
-// Aout (+ ex[0], ld exi[3]) = the A row; ex[1] / ex[2] = reward / not_done (record offset
-// exi[1], exi[1] + 1); problem 0 records the drawn rows.
+// A problem's first column tile also stores its rows for the later stages (no extra loads): the
+// A row to Aout and ring_l0::kRowCopy2, reward / not_done to kReward / kNotDone; problem 0 records
+// the drawn rows.
 
 // reward (lane 0) / not_done (lane 1) destination of the sample: a select between the two
-// scalar fields.  Indexed as P.ex[1 + lane], the pointer was fetched by a VECTOR load of the
+// scalar fields.  Indexed as P.ex[kReward + lane], the pointer was fetched by a VECTOR load of the
 // kernel arguments whose vmcnt(0) drained every weight load in flight (the n-tile-0 workgroups
 // of F_fwd01 ran ~3 us behind the rest).
 __device__ __forceinline__ float* rw_ptr(const GemmProb& P, int lane) {
-  float* r0 = P.ex[1];
-  float* r1 = P.ex[2];
+  using namespace ring_l0;
+  float* r0 = P.ex[kReward];
+  float* r1 = P.ex[kNotDone];
   asm volatile("" : "+s"(r0), "+s"(r1));   // pinned in SGPRs: the select below is a v_cndmask
   return lane == 0 ? r0 : r1;
 }
 template <int RPW>
 __device__ __forceinline__ void pro_gather(const GemmProb& P, const RingSide& rs, float* smem, const Ctx& c,
                                            int pi) {
+  using namespace ring_l0;
   const uint64_t step = (uint64_t)(rs.ctr->total_it + 1);
   const uint64_t n = (uint64_t)*rs.d_size;
   int64_t idx[RPW];
@@ -297,8 +299,8 @@ __device__ __forceinline__ void pro_gather(const GemmProb& P, const RingSide& rs
     rw[r] = 0.f;
     if (idx[r] >= 0) {
       const float* rec = rs.data + (size_t)idx[r] * rs.rec;
-      rv_load_u(x[r], rec + P.exi[0], P.Kreal, c.lane);
-      if (t0 && c.lane < 2 && rw_ptr(P, c.lane)) rw[r] = gld(rec + P.exi[1] + c.lane);
+      rv_load_u(x[r], rec + P.exi[kRecOff], P.Kreal, c.lane);
+      if (t0 && c.lane < 2 && rw_ptr(P, c.lane)) rw[r] = gld(rec + P.exi[kRecOffRw] + c.lane);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[r][j] = 0.f;
@@ -315,7 +317,7 @@ __device__ __forceinline__ void pro_gather(const GemmProb& P, const RingSide& rs
       const int col = rcol(c.lane, j);
       if (col < P.Kreal) {
         if (P.Aout) gst(P.Aout + (size_t)grow * P.ldao + col, x[r][j]);
-        if (P.ex[0]) gst(P.ex[0] + (size_t)grow * P.exi[3] + col, x[r][j]);
+        if (P.ex[kRowCopy2]) gst(P.ex[kRowCopy2] + (size_t)grow * P.exi[kLdRowCopy2] + col, x[r][j]);
       }
     }
     if (c.lane < 2 && rw_ptr(P, c.lane)) gst(rw_ptr(P, c.lane) + grow, rw[r]);
@@ -336,7 +338,8 @@ struct L0X {
 };
 template <bool GATHER>
 __device__ __forceinline__ void l0_load_x(const GemmProb& P, const RingSide& rs, const Ctx& c, L0X& X) {
-  const int K0 = P.exi[6];
+  using namespace ring_l0;
+  const int K0 = P.exi[kK0];
   const int i = c.lane & 31, h = c.lane >> 5;
   const bool t0 = c.nt == 0;
   uint64_t step = 0, n = 0;
@@ -366,8 +369,8 @@ __device__ __forceinline__ void l0_load_x(const GemmProb& P, const RingSide& rs,
     if constexpr (GATHER) {
       const int64_t idx = X.idx[rr] >= 0 ? X.idx[rr] : 0;
       const float* rec = rs.data + (size_t)idx * rs.rec;
-      X.x[rr] = gld(rec + P.exi[0] + (valid ? col : 0));
-      X.rw[rr] = t0 ? gld(rec + P.exi[1] + (i & 1)) : 0.f;
+      X.x[rr] = gld(rec + P.exi[kRecOff] + (valid ? col : 0));
+      X.rw[rr] = t0 ? gld(rec + P.exi[kRecOffRw] + (i & 1)) : 0.f;
     } else {
       X.x[rr] = gld(P.A + (size_t)grow * P.lda + col);  // input rows are >= 32 wide (zero pads)
     }
@@ -378,7 +381,8 @@ __device__ __forceinline__ void l0_load_x(const GemmProb& P, const RingSide& rs,
 template <bool GATHER>
 __device__ __forceinline__ void l0_put_x(const GemmProb& P, const RingSide& rs, float* xs, const Ctx& c, int pi,
                                          const L0X& X) {
-  const int K0 = P.exi[6];
+  using namespace ring_l0;
+  const int K0 = P.exi[kK0];
   const int i = c.lane & 31, h = c.lane >> 5;
   const bool t0 = c.nt == 0;
   const int col = i;
@@ -391,8 +395,8 @@ __device__ __forceinline__ void l0_put_x(const GemmProb& P, const RingSide& rs, 
     if constexpr (GATHER) {
       if (t0) {
         if (valid) {
-          if (P.ex[3]) gst(P.ex[3] + (size_t)grow * P.exi[8] + col, xv);
-          if (P.ex[0]) gst(P.ex[0] + (size_t)grow * P.exi[3] + col, xv);
+          if (P.ex[kRowCopy]) gst(P.ex[kRowCopy] + (size_t)grow * P.exi[kLdRowCopy] + col, xv);
+          if (P.ex[kRowCopy2]) gst(P.ex[kRowCopy2] + (size_t)grow * P.exi[kLdRowCopy2] + col, xv);
         }
         if (i < 2 && rw_ptr(P, i)) gst(rw_ptr(P, i) + grow, X.idx[rr] >= 0 ? X.rw[rr] : 0.f);
         if (pi == 0 && rs.idx_out && i == 0 && grow < P.B) rs.idx_out[grow] = X.idx[rr];
@@ -403,7 +407,7 @@ __device__ __forceinline__ void l0_put_x(const GemmProb& P, const RingSide& rs, 
 
 // k offset of lane half h in the layer-0 operands: 12h when the input fits in 24 columns (the x
 // rows' and W0 rows' columns 24..31 are zero pads, so a half's 16-wide read past k = 24 reads 0)
-__device__ __forceinline__ int l0_koff(const GemmProb& P, int h) { return (P.exi[6] <= 24 ? 12 : 16) * h; }
+__device__ __forceinline__ int l0_koff(const GemmProb& P, int h) { return (P.exi[ring_l0::kK0] <= 24 ? 12 : 16) * h; }
 
 // Stage 2: Z0 = X * W0^T on MFMA (wave w: layer-0 column tiles w and w + 8), + b0, ReLU, into the
 // layer-1 A buffer (LDS, [32][S]); n-tile 0 also stores H0 (the backward's post-ReLU rows).
@@ -412,9 +416,10 @@ __device__ __forceinline__ int l0_koff(const GemmProb& P, int h) { return (P.exi
 // earlier variant that selected between layouts on the loaded data waited early: slower.)
 __device__ __forceinline__ void l0_mfma(const GemmProb& P, const float* xs, float* smem, float* h0s, const Ctx& c,
                                         const float (&w0)[2][16], const float (&b0)[2]) {
+  using namespace ring_l0;
   const int i = c.lane & 31, h = c.lane >> 5;
-  const int n0t = P.exi[5] >> 5;
-  const bool k24 = P.exi[6] <= 24;
+  const int n0t = P.exi[kN0p] >> 5;
+  const bool k24 = P.exi[kK0] <= 24;
   const float* arow = xs + i * kL0XS + l0_koff(P, h);
   float av[16];
 #pragma unroll
@@ -422,7 +427,7 @@ __device__ __forceinline__ void l0_mfma(const GemmProb& P, const float* xs, floa
     const float4 v = *reinterpret_cast<const float4*>(arow + 4 * q);
     av[4 * q + 0] = v.x; av[4 * q + 1] = v.y; av[4 * q + 2] = v.z; av[4 * q + 3] = v.w;
   }
-  const bool keep = P.ex[10] && P.norm;   // H0 kept in LDS for l0_store_rows (LN overwrites smem)
+  const bool keep = P.ex[kH0] && P.norm;   // H0 kept in LDS for l0_store_rows (LN overwrites smem)
   // both tiles' MFMA chains first (two accumulators), then the epilogues, with the uniform `keep`
   // hoisted out of the element loop (inside it, it compiled to a branch per element)
   f32x16 acc[2];
@@ -486,7 +491,8 @@ __device__ __forceinline__ void l0_ln(const GemmProb& P, float* smem, const Ctx&
 // the rest (F_fwd01, tools/tl_probe.py).
 template <int NT>
 __device__ __forceinline__ void l0_store_rows(const GemmProb& P, const float* smem, const float* h0s, const Ctx& c) {
-  float* H0 = P.ex[10];
+  using namespace ring_l0;
+  float* H0 = P.ex[kH0];
   float* U0 = P.norm ? P.Aout : nullptr;
   if (!H0 && !U0) return;
   const float* hsrc = P.norm ? h0s : smem;          // no LN: the A buffer is H0
@@ -495,7 +501,7 @@ __device__ __forceinline__ void l0_store_rows(const GemmProb& P, const float* sm
   for (int e = threadIdx.x; e < 32 * per; e += NT) {
     const int row = e / per, q = 4 * (q0 + e % per);
     const size_t grow = (size_t)(c.m0 + row);
-    if (H0) gst4(H0 + grow * P.exi[5] + q, *reinterpret_cast<const float4*>(hsrc + row * c.S + q));
+    if (H0) gst4(H0 + grow * P.exi[kN0p] + q, *reinterpret_cast<const float4*>(hsrc + row * c.S + q));
     if (U0) gst4(U0 + grow * P.ldao + q, *reinterpret_cast<const float4*>(smem + row * c.S + q));
   }
 }
@@ -509,12 +515,7 @@ struct RowCtx {
 };
 
 // ---- policy heads: target smoothing (TD3_featured.py:131-137) / pi(s) = ma*tanh (:47-48) --
-// ex[0]=H3 ex[1]=gamma3 ex[2]=beta3 ex[3]=W4 ex[4]=b4 ex[5]=noise
-// out: ex[6]=critic input rows (action columns at sd..) ex[7]=T ex[8]=U3 ex[9]=stats3
-// exi[0]=K3 exi[1]=ld3 exi[2]=ldw4 exi[3]=ld_out exi[4]=gen_noise exi[5]=ad exi[6]=sd exi[7]=ldn
-// exi[8]=target (1: smoothing; 0: policy) exi[9]=clamp a' to +-max_action (TD3_featured :135-137;
-// TD3_particles :179-181 has no clamp)   ex[10]=second critic-input buffer for a' (nullable)
-// exf[0]=max_action (1 for TD3_particles: tanh output, :68) exf[1]=policy_noise exf[2]=noise_clip
+// (operands: policy_head, kernels.h)
 constexpr int kHeadRegs = 8;   // head outputs kept in registers (wider heads loop)
 
 // Wide heads (action width > kHeadRegs; Humanoid: 17).  Requested block by block, the head weight
@@ -553,19 +554,21 @@ __device__ __forceinline__ void wide_stage(float4* dst, const float4* a, int n1,
 
 template <bool NORM, int RW = 1>
 __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx& c) {
+  using namespace policy_head;
   // every field in one scalar-load batch, and the step counter (Philox noise) requested with
   // the row: left alone, the compiler fetched fields where used (a chain of kernel-argument round
   // trips) and the counter after the head's dot products (one more memory round trip at the tail)
-  asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.ex[5]),
-               "s"(P.ex[6]), "s"(P.ex[7]), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.ex[10]), "s"(P.exi[0]),
-               "s"(P.exi[1]), "s"(P.exi[2]), "s"(P.exi[3]), "s"(P.exi[4]), "s"(P.exi[5]), "s"(P.exi[6]),
-               "s"(P.exi[7]), "s"(P.exi[8]), "s"(P.exi[9]), "s"(P.exf[0]), "s"(P.exf[1]), "s"(P.exf[2]),
+  asm volatile("" ::"s"(P.ex[kH3]), "s"(P.ex[kGamma3]), "s"(P.ex[kBeta3]), "s"(P.ex[kW4]), "s"(P.ex[kB4]),
+               "s"(P.ex[kNoise]), "s"(P.ex[kOut]), "s"(P.ex[kTanh]), "s"(P.ex[kU3]), "s"(P.ex[kStats3]),
+               "s"(P.ex[kOut2]), "s"(P.exi[kK3]), "s"(P.exi[kLd3]), "s"(P.exi[kLdw4]), "s"(P.exi[kLdOut]),
+               "s"(P.exi[kGenNoise]), "s"(P.exi[kAd]), "s"(P.exi[kActCol]), "s"(P.exi[kLdNoise]), "s"(P.exi[kTarget]),
+               "s"(P.exi[kClamp]), "s"(P.exf[kMaxAction]), "s"(P.exf[kPolicyNoise]), "s"(P.exf[kNoiseClip]),
                "s"(P.seed), "s"(P.ctr), "s"(P.B), "s"(P.tile_begin));
-  const int K3 = P.exi[0], ld3 = P.exi[1], ldw4 = P.exi[2];
-  const int ad = P.exi[5], sd = P.exi[6];
-  const bool target = P.exi[8] != 0;
-  const float ma = P.exf[0];
-  const bool gen = target && P.exi[4];
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3], ldw4 = P.exi[kLdw4];
+  const int ad = P.exi[kAd], sd = P.exi[kActCol];
+  const bool target = P.exi[kTarget] != 0;
+  const float ma = P.exf[kMaxAction];
+  const bool gen = target && P.exi[kGenNoise];
   // the counter (ctr is always set, td3.hip) by an ordinary relaxed load whose address carries a
   // lane-dependent zero (mbcnt with an empty mask): a divergent load, so the value lands in VGPRs
   // and the compiler's own wait placement defers it to the Philox draw.  Left uniform, it is a
@@ -573,19 +576,19 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
   const int64_t* ctrp = &P.ctr->total_it + __builtin_amdgcn_mbcnt_lo(0u, 0u);
   const uint64_t stepv = (uint64_t)__hip_atomic_load(ctrp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   float x[1][8], g[8], bb[8], mean[1], rstd[1];
-  rv_load(x[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
   if (NORM) {
-    rv_load(g, P.ex[1], ld3, c.lane);
-    rv_load(bb, P.ex[2], ld3, c.lane);
+    rv_load(g, P.ex[kGamma3], ld3, c.lane);
+    rv_load(bb, P.ex[kBeta3], ld3, c.lane);
   }
   float nz = 0.f;
-  if (target && !P.exi[4] && c.lane < ad) nz = gld(P.ex[5] + ((size_t)c.row * P.exi[7] + c.lane));
+  if (target && !P.exi[kGenNoise] && c.lane < ad) nz = gld(P.ex[kNoise] + ((size_t)c.row * P.exi[kLdNoise] + c.lane));
   float mine = 0.f;                       // lane o keeps head output o
   if (RW > 1 && P.tile_begin) {           // wide head: W4's ad rows staged in LDS (wide_stage)
     extern __shared__ float4 row_lds4[];
-    const float bl = gld(P.ex[4] + (c.lane < ad ? c.lane : 0));
-    wide_stage<64 * RW>(row_lds4, reinterpret_cast<const float4*>(P.ex[3]), ad * ldw4 / 4,
-               reinterpret_cast<const float4*>(P.ex[3]), 0);
+    const float bl = gld(P.ex[kB4] + (c.lane < ad ? c.lane : 0));
+    wide_stage<64 * RW>(row_lds4, reinterpret_cast<const float4*>(P.ex[kW4]), ad * ldw4 / 4,
+               reinterpret_cast<const float4*>(P.ex[kW4]), 0);
     const float* hw = reinterpret_cast<const float*>(row_lds4);
     opaque8(x[0]); opaque8(g); opaque8(bb);
     TL_MARK(5);
@@ -610,8 +613,8 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
 #pragma unroll
   for (int o = 0; o < kHeadRegs; ++o) {
     const int oo = o < ad ? o : 0;
-    rv_load(w4[o], P.ex[3] + (size_t)oo * ldw4, ldw4, c.lane);
-    b4v[o] = gld(P.ex[4] + oo);
+    rv_load(w4[o], P.ex[kW4] + (size_t)oo * ldw4, ldw4, c.lane);
+    b4v[o] = gld(P.ex[kB4] + oo);
   }
   TL_MARK(5);
   TL_FINE(6);
@@ -632,8 +635,8 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
 #pragma unroll
     for (int o = 0; o < kHeadRegs; ++o) {
       const int oo = ob + o < ad ? ob + o : 0;
-      rv_load(wb[o], P.ex[3] + (size_t)oo * ldw4, ldw4, c.lane);
-      bv[o] = gld(P.ex[4] + oo);
+      rv_load(wb[o], P.ex[kW4] + (size_t)oo * ldw4, ldw4, c.lane);
+      bv[o] = gld(P.ex[kB4] + oo);
     }
     float pb[kHeadRegs];
 #pragma unroll
@@ -647,10 +650,10 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
   }
   }
   if (!target) {
-    if (NORM) rv_store(P.ex[8] + (size_t)c.row * ld3, ld3, c.lane, x[0]);
+    if (NORM) rv_store(P.ex[kU3] + (size_t)c.row * ld3, ld3, c.lane, x[0]);
     if (NORM && c.lane == 0) {
-      gst(P.ex[9] + c.row, mean[0]);
-      gst(P.ex[9] + (c.Bp + c.row), rstd[0]);
+      gst(P.ex[kStats3] + c.row, mean[0]);
+      gst(P.ex[kStats3] + (c.Bp + c.row), rstd[0]);
     }
   }
   TL_MARK(7);
@@ -665,111 +668,18 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
       float g4[4];
       philox_normal4(P.seed, stepv, kStreamNoise, (uint32_t)(c.row * 8 + (o >> 2)), g4);
       z = g4[o & 3];
-      gst(P.ex[5] + ((size_t)c.row * P.exi[7] + o), z);
+      gst(P.ex[kNoise] + ((size_t)c.row * P.exi[kLdNoise] + o), z);
     }
-    float n = z * P.exf[1];
-    n = fminf(fmaxf(n, -P.exf[2]), P.exf[2]);
+    float n = z * P.exf[kPolicyNoise];
+    n = fminf(fmaxf(n, -P.exf[kNoiseClip]), P.exf[kNoiseClip]);
     const float v = ma * th + n;
-    a = P.exi[9] ? fminf(fmaxf(v, -ma), ma) : v;
+    a = P.exi[kClamp] ? fminf(fmaxf(v, -ma), ma) : v;
   } else {
     a = ma * th;
-    gst(P.ex[7] + ((size_t)c.row * 32 + o), th);
+    gst(P.ex[kTanh] + ((size_t)c.row * 32 + o), th);
   }
-  gst(P.ex[6] + ((size_t)c.row * P.exi[3] + sd + o), live ? a : 0.f);
-  if (P.ex[10]) gst(P.ex[10] + ((size_t)c.row * P.exi[3] + sd + o), live ? a : 0.f);
-}
-
-// ---- clipped double-Q target + critic mse backward into LN3 of Q_j -----------------------
-// ex[0..2]=H3 of (target q1, target q2, online q_j)  ex[3..5]=gamma3  ex[6..8]=beta3
-// ex[9..11]=w4 (row 0)  ex[12..14]=b4  ex[15]=reward  ex[16]=not_done
-// out: ex[17]=dZ4_j (ld 32) ex[18]=dU3_j ex[19]=U3_j ex[20]=stats3_j ex[21]=y ex[22]=sqerr_j
-//      ex[23]=Q_j  Aout=dZ3_j
-// exi[0]=K3 exi[1]=ld3 exi[2]=j   exf[0]=discount exf[1]=2/B
-template <bool NORM>
-__device__ __forceinline__ void row_critic_loss(const GemmProb& P, const RowCtx& c) {
-  // every field in one scalar-load batch (left alone: a kernel-argument round trip per pointer)
-  asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.ex[5]),
-               "s"(P.ex[6]), "s"(P.ex[7]), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.ex[10]), "s"(P.ex[11]),
-               "s"(P.ex[12]), "s"(P.ex[13]), "s"(P.ex[14]), "s"(P.ex[15]), "s"(P.ex[16]));
-  asm volatile("" ::"s"(P.ex[17]), "s"(P.ex[18]), "s"(P.ex[19]), "s"(P.ex[20]), "s"(P.ex[21]), "s"(P.ex[22]),
-               "s"(P.ex[23]), "s"(P.exi[0]), "s"(P.exi[1]), "s"(P.exi[2]), "s"(P.exf[0]), "s"(P.exf[1]),
-               "s"(P.Aout), "s"(P.ldao), "s"(P.B));
-  const int K3 = P.exi[0], ld3 = P.exi[1], j = P.exi[2];
-  float x0[1][8], x1[1][8], xq[1][8], h[1][8], g[3][8], bb[3][8], w[3][8];
-  rv_load(x0[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
-  rv_load(x1[0], P.ex[1] + (size_t)c.row * ld3, ld3, c.lane);
-  rv_load(xq[0], P.ex[2] + (size_t)c.row * ld3, ld3, c.lane);
-#pragma unroll
-  for (int n = 0; n < 3; ++n) {
-    if (NORM) {
-      rv_load(g[n], P.ex[3 + n], ld3, c.lane);
-      rv_load(bb[n], P.ex[6 + n], ld3, c.lane);
-    }
-    rv_load(w[n], P.ex[9 + n], ld3, c.lane);
-  }
-  const float b40 = gld(P.ex[12]), b41 = gld(P.ex[13]), b4q = gld(P.ex[14]);
-  const float rw = gld(P.ex[15] + c.row), nd = gld(P.ex[16] + c.row);
-  __builtin_amdgcn_sched_barrier(0);     // every load requested before the first use
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) h[0][jj] = xq[0][jj];
-  float m0[1], s0[1], m1[1], s1[1], mq[1], sq[1];
-  if (NORM) {
-    ln_fwd_rows<1>(x0, g[0], bb[0], K3, c.lane, m0, s0);
-    ln_fwd_rows<1>(x1, g[1], bb[1], K3, c.lane, m1, s1);
-    ln_fwd_rows<1>(xq, g[2], bb[2], K3, c.lane, mq, sq);
-  }
-  const float d0 = rv_pdot(x0[0], w[0], K3, c.lane);
-  const float d1 = rv_pdot(x1[0], w[1], K3, c.lane);
-  const float dq = rv_pdot(xq[0], w[2], K3, c.lane);
-  const float tq0 = wsum(d0) + b40, tq1 = wsum(d1) + b41, q = wsum(dq) + b4q;
-  const float y = rw + (nd * P.exf[0]) * fminf(tq0, tq1);                  // :141-142
-  const float d = q - y;
-  const bool live = c.row < P.B;
-  const float gq = live ? P.exf[1] * d : 0.f;                              // mse_loss bwd (:148)
-  if (c.lane == 0) {
-    gst(P.ex[17] + ((size_t)c.row * 32), gq);
-    gst(P.ex[23] + c.row, q);
-    gst(P.ex[22] + c.row, live ? d * d : 0.f);
-    if (j == 0) gst(P.ex[21] + c.row, y);
-    if (NORM) {
-      gst(P.ex[20] + c.row, mq[0]);
-      gst(P.ex[20] + (c.Bp + c.row), sq[0]);
-    }
-  }
-  float gu[1][8];
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) gu[0][jj] = gq * w[2][jj];
-  rv_store(P.ex[18] + (size_t)c.row * ld3, ld3, c.lane, gu[0]);
-  if (NORM) rv_store(P.ex[19] + (size_t)c.row * ld3, ld3, c.lane, xq[0]);
-  ln_bwd_rows<1>(gu, h, g[2], mq, sq, K3, c.lane, NORM);
-  rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu[0]);
-}
-
-// ---- actor loss -mean Q1(s, pi(s)) backward into LN3 of Q1 (:159) ------------------------
-// ex[0]=H3 ex[1]=gamma3 ex[2]=beta3 ex[3]=w4 ex[4]=b4 out ex[5]=Q values, Aout=dZ3
-// exi[0]=K3 exi[1]=ld3   exf[0]=-1/B
-template <bool NORM>
-__device__ __forceinline__ void row_actor_loss(const GemmProb& P, const RowCtx& c) {
-  const int K3 = P.exi[0], ld3 = P.exi[1];
-  float x[1][8], h[1][8], g[8], bb[8], w[8], mean[1], rstd[1];
-  rv_load(x[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
-  if (NORM) {
-    rv_load(g, P.ex[1], ld3, c.lane);
-    rv_load(bb, P.ex[2], ld3, c.lane);
-  }
-  rv_load(w, P.ex[3], ld3, c.lane);
-  const float b4 = gld(P.ex[4]);
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) h[0][jj] = x[0][jj];
-  if (NORM) ln_fwd_rows<1>(x, g, bb, K3, c.lane, mean, rstd);
-  const float q = wsum(rv_pdot(x[0], w, K3, c.lane)) + b4;
-  if (c.lane == 0) gst(P.ex[5] + c.row, q);
-  const float gq = c.row < P.B ? P.exf[0] : 0.f;
-  float gu[1][8];
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) gu[0][jj] = gq * w[jj];
-  ln_bwd_rows<1>(gu, h, g, mean, rstd, K3, c.lane, NORM);
-  rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu[0]);
+  gst(P.ex[kOut] + ((size_t)c.row * P.exi[kLdOut] + sd + o), live ? a : 0.f);
+  if (P.ex[kOut2]) gst(P.ex[kOut2] + ((size_t)c.row * P.exi[kLdOut] + sd + o), live ? a : 0.f);
 }
 
 // W[:, s0 .. s0+kHeadRegs): those columns of the 8 W rows a lane owns (rcol), as two float4 loads
@@ -793,47 +703,45 @@ __device__ __forceinline__ void head_cols(const float* W, int ldw, int s0, int l
 }
 
 // ---- dQ1/da through Q1's first layer, then the actor's head and LN3 backward -------------
-// ex[0]=dU0 of Q1(s,pi) ex[1]=H0 of Q1(s,pi) ex[2]=stats0 ex[3]=gamma0(q1) ex[4]=W1(q1)
-// ex[5]=T (tanh out) ex[6]=W4(actor) ex[7]=H3(actor) ex[8]=stats3(actor) ex[9]=gamma3(actor)
-// out: ex[10]=dZ4 actor (ld 32) ex[11]=dU3 actor  Aout=dZ3 actor
-// exi[0]=K0 exi[1]=ld0 exi[2]=ldw1 exi[3]=sd exi[4]=ad exi[5]=K3 exi[6]=ld3 exi[7]=ldw4
-// exf[0]=max_action
+// (operands: actor_head_bwd, kernels.h)
 template <bool NORM, int RW = 1>
 __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowCtx& c) {
+  using namespace actor_head_bwd;
   // every field in one scalar-load batch (left alone, the compiler requested them where used, in
   // dependent kernel-argument round trips between the row's loads)
-  asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.ex[5]),
-               "s"(P.ex[6]), "s"(P.ex[7]), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.ex[10]), "s"(P.ex[11]),
-               "s"(P.ex[12]), "s"(P.exi[0]), "s"(P.exi[1]), "s"(P.exi[2]), "s"(P.exi[3]), "s"(P.exi[4]),
-               "s"(P.exi[5]), "s"(P.exi[6]), "s"(P.exi[7]), "s"(P.exi[8]), "s"(P.exf[0]), "s"(P.Aout),
-               "s"(P.ldao), "s"(P.B), "s"(P.tile_begin));
-  const int K0 = P.exi[0], ld0 = P.exi[1], ldw1 = P.exi[2], sd = P.exi[3], ad = P.exi[4];
-  const int K3 = P.exi[5], ld3 = P.exi[6], ldw4 = P.exi[7];
-  const float ma = P.exf[0];
+  asm volatile("" ::"s"(P.ex[kDU0]), "s"(P.ex[kH0]), "s"(P.ex[kStats0]), "s"(P.ex[kGamma0]), "s"(P.ex[kW1]),
+               "s"(P.ex[kTanh]), "s"(P.ex[kW4]), "s"(P.ex[kH3]), "s"(P.ex[kStats3]), "s"(P.ex[kGamma3]),
+               "s"(P.ex[kDZ4]), "s"(P.ex[kDU3]), "s"(P.ex[kW1T]), "s"(P.exi[kK0]), "s"(P.exi[kLd0]),
+               "s"(P.exi[kLdw1]), "s"(P.exi[kActCol]), "s"(P.exi[kAd]), "s"(P.exi[kK3]), "s"(P.exi[kLd3]),
+               "s"(P.exi[kLdw4]), "s"(P.exi[kLdW1T]), "s"(P.exf[kMaxAction]), "s"(P.Aout), "s"(P.ldao), "s"(P.B),
+               "s"(P.tile_begin));
+  const int K0 = P.exi[kK0], ld0 = P.exi[kLd0], ldw1 = P.exi[kLdw1], sd = P.exi[kActCol], ad = P.exi[kAd];
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3], ldw4 = P.exi[kLdw4];
+  const float ma = P.exf[kMaxAction];
   float gu0[1][8], h0[1][8], h3[1][8], g0[8], g3[8], mn0[1], rs0[1], mn3[1], rs3[1];
   float w1[kHeadRegs][8], w4[kHeadRegs][8];
-  rv_load(gu0[0], P.ex[0] + (size_t)c.row * ld0, ld0, c.lane);
-  rv_load(h0[0], P.ex[1] + (size_t)c.row * ld0, ld0, c.lane);
-  rv_load(h3[0], P.ex[7] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(gu0[0], P.ex[kDU0] + (size_t)c.row * ld0, ld0, c.lane);
+  rv_load(h0[0], P.ex[kH0] + (size_t)c.row * ld0, ld0, c.lane);
+  rv_load(h3[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
   if (NORM) {
-    rv_load(g0, P.ex[3], ld0, c.lane);
-    rv_load(g3, P.ex[9], ld3, c.lane);
-    mn0[0] = gld(P.ex[2] + c.row);
-    rs0[0] = gld(P.ex[2] + (c.Bp + c.row));
-    mn3[0] = gld(P.ex[8] + c.row);
-    rs3[0] = gld(P.ex[8] + (c.Bp + c.row));
+    rv_load(g0, P.ex[kGamma0], ld0, c.lane);
+    rv_load(g3, P.ex[kGamma3], ld3, c.lane);
+    mn0[0] = gld(P.ex[kStats0] + c.row);
+    rs0[0] = gld(P.ex[kStats0] + (c.Bp + c.row));
+    mn3[0] = gld(P.ex[kStats3] + c.row);
+    rs3[0] = gld(P.ex[kStats3] + (c.Bp + c.row));
   } else {
     mn0[0] = mn3[0] = 0.f;
     rs0[0] = rs3[0] = 1.f;
   }
-  const float tl = c.lane < ad ? gld(P.ex[5] + ((size_t)c.row * 32 + c.lane)) : 0.f;
-  // W1[:, sd+o], the action columns: rows of the transposed copy when the step keeps one (ex[12],
-  // row length exi[8]: coalesced, the same elements per lane), else strided column reads
-  const float* w1t = P.ex[12];
+  const float tl = c.lane < ad ? gld(P.ex[kTanh] + ((size_t)c.row * 32 + c.lane)) : 0.f;
+  // W1[:, sd+o], the action columns: rows of the transposed copy when the step keeps one (kW1T,
+  // row length kLdW1T: coalesced, the same elements per lane), else strided column reads
+  const float* w1t = P.ex[kW1T];
   if (RW > 1 && P.tile_begin) {     // wide head (wide_stage): the transposed W1 rows, then W4's, in LDS
     extern __shared__ float4 row_lds4[];
-    const int n1 = ad * P.exi[8] / 4;
-    wide_stage<64 * RW>(row_lds4, reinterpret_cast<const float4*>(w1t), n1, reinterpret_cast<const float4*>(P.ex[6]),
+    const int n1 = ad * P.exi[kLdW1T] / 4;
+    wide_stage<64 * RW>(row_lds4, reinterpret_cast<const float4*>(w1t), n1, reinterpret_cast<const float4*>(P.ex[kW4]),
                ad * ldw4 / 4);
     const float* hw1 = reinterpret_cast<const float*>(row_lds4);
     const float* hw4 = hw1 + (size_t)4 * n1;
@@ -849,7 +757,7 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
 #pragma unroll
       for (int o = 0; o < kHeadRegs; ++o) {
         float w[8];
-        rv_load_lds(w, hw1 + (size_t)(ob + o < ad ? ob + o : 0) * P.exi[8], K0, c.lane);
+        rv_load_lds(w, hw1 + (size_t)(ob + o < ad ? ob + o : 0) * P.exi[kLdW1T], K0, c.lane);
         pb[o] = rv_pdot(gu0[0], w, K0, c.lane);
       }
 #pragma unroll
@@ -858,28 +766,28 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
           const float ga = wsum(pb[o]);                               // dL/da_o
           const float t = __shfl(tl, ob + o, 64);
           const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;   // max_action*tanh bwd
-          if (c.lane == 0) gst(P.ex[10] + ((size_t)c.row * 32 + ob + o), gz4);
+          if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + ob + o), gz4);
           float w4r[8];
           rv_load_lds(w4r, hw4 + (size_t)(ob + o) * ldw4, ldw4, c.lane);
 #pragma unroll
           for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4r[jj];
         }
     }
-    rv_store(P.ex[11] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
+    rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
     ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);        // dZ3 of the actor
     rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
     return;
   }
   if (w1t) {
 #pragma unroll
-    for (int o = 0; o < kHeadRegs; ++o) rv_load(w1[o], w1t + (size_t)(o < ad ? o : 0) * P.exi[8], K0, c.lane);
+    for (int o = 0; o < kHeadRegs; ++o) rv_load(w1[o], w1t + (size_t)(o < ad ? o : 0) * P.exi[kLdW1T], K0, c.lane);
   } else {
-    head_cols(P.ex[4], ldw1, sd, ad, c.lane, w1);
+    head_cols(P.ex[kW1], ldw1, sd, ad, c.lane, w1);
   }
 #pragma unroll
   for (int o = 0; o < kHeadRegs; ++o) {
     const int oo = o < ad ? o : 0;
-    rv_load(w4[o], P.ex[6] + (size_t)oo * ldw4, ldw4, c.lane);
+    rv_load(w4[o], P.ex[kW4] + (size_t)oo * ldw4, ldw4, c.lane);
   }
   ln_bwd_rows<1>(gu0, h0, g0, mn0, rs0, K0, c.lane, NORM);       // dZ0 of Q1 (pads -> 0)
   const bool live = c.row < P.B;
@@ -895,7 +803,7 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
       const float ga = wsum(part[o]);                                 // dL/da_o
       const float t = __shfl(tl, o, 64);
       const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;       // max_action*tanh bwd
-      if (c.lane == 0) gst(P.ex[10] + ((size_t)c.row * 32 + o), gz4);
+      if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + o), gz4);
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4[o][jj];
     }
@@ -906,14 +814,14 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
     if (w1t) {
 #pragma unroll
       for (int o = 0; o < kHeadRegs; ++o)
-        rv_load(w1b[o], w1t + (size_t)(ob + o < ad ? ob + o : 0) * P.exi[8], K0, c.lane);
+        rv_load(w1b[o], w1t + (size_t)(ob + o < ad ? ob + o : 0) * P.exi[kLdW1T], K0, c.lane);
     } else {
-      head_cols(P.ex[4], ldw1, sd + ob, ad - ob, c.lane, w1b);
+      head_cols(P.ex[kW1], ldw1, sd + ob, ad - ob, c.lane, w1b);
     }
 #pragma unroll
     for (int o = 0; o < kHeadRegs; ++o) {
       const int oo = ob + o < ad ? ob + o : 0;
-      rv_load(w4b[o], P.ex[6] + (size_t)oo * ldw4, ldw4, c.lane);
+      rv_load(w4b[o], P.ex[kW4] + (size_t)oo * ldw4, ldw4, c.lane);
     }
     float pb[kHeadRegs];
 #pragma unroll
@@ -924,12 +832,12 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
         const float ga = wsum(pb[o]);
         const float t = __shfl(tl, ob + o, 64);
         const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;
-        if (c.lane == 0) gst(P.ex[10] + ((size_t)c.row * 32 + ob + o), gz4);
+        if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + ob + o), gz4);
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4b[o][jj];
       }
   }
-  rv_store(P.ex[11] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
+  rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
   ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);        // dZ3 of the actor
   rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
 }
@@ -939,27 +847,24 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
 // TD3_particles.py:91); y = r + not_done*discount*min(Q1', Q2') broadcasts over them (:183-189)
 // and F.mse_loss averages over B*A.  Values / targets are kept as [Bp][32] rows.
 
-// ex[0..2]=H3 of (target q1, target q2 (= target q1 when CDQ is off), online q_j)
-// ex[3..5]=gamma3 ex[6..8]=beta3 ex[9..11]=W4 [nq][ldw4] ex[12..14]=b4 ex[15]=reward ex[16]=not_done
-// out: ex[17]=dZ4_j (ld 32) ex[18]=dU3_j ex[19]=U3_j ex[20]=stats3_j ex[21]=y [Bp][32]
-//      ex[22]=sqerr_j (sum over outputs) ex[23]=Q_j [Bp][32]   Aout=dZ3_j
-// exi[0]=K3 exi[1]=ld3 exi[2]=j exi[3]=nq exi[4]=ldw4 exi[5]=cdq   exf[0]=discount exf[1]=2/(B*nq)
+// (operands: critic_loss_p, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_critic_loss_p(const GemmProb& P, const RowCtx& c) {
-  const int K3 = P.exi[0], ld3 = P.exi[1], j = P.exi[2], nq = P.exi[3], ldw4 = P.exi[4];
-  const bool cdq = P.exi[5] != 0;
+  using namespace critic_loss_p;
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3], j = P.exi[kJ], nq = P.exi[kNq], ldw4 = P.exi[kLdw4];
+  const bool cdq = P.exi[kCdq] != 0;
   float x0[1][8], x1[1][8], xq[1][8], h[1][8], g[3][8], bb[3][8];
-  rv_load(x0[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
-  rv_load(x1[0], P.ex[1] + (size_t)c.row * ld3, ld3, c.lane);
-  rv_load(xq[0], P.ex[2] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x0[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x1[0], P.ex[kH3 + 1] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(xq[0], P.ex[kH3 + 2] + (size_t)c.row * ld3, ld3, c.lane);
   if (NORM) {
 #pragma unroll
     for (int n = 0; n < 3; ++n) {
-      rv_load(g[n], P.ex[3 + n], ld3, c.lane);
-      rv_load(bb[n], P.ex[6 + n], ld3, c.lane);
+      rv_load(g[n], P.ex[kGamma3 + n], ld3, c.lane);
+      rv_load(bb[n], P.ex[kBeta3 + n], ld3, c.lane);
     }
   }
-  const float rw = gld(P.ex[15] + c.row), nd = gld(P.ex[16] + c.row);
+  const float rw = gld(P.ex[kReward] + c.row), nd = gld(P.ex[kNotDone] + c.row);
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) h[0][jj] = xq[0][jj];
   float m0[1], s0[1], m1[1], s1[1], mq[1], sq[1];
@@ -978,61 +883,61 @@ __device__ __forceinline__ void row_critic_loss_p(const GemmProb& P, const RowCt
   float se = 0.f;
   for (int o = 0; o < nq; ++o) {
     float w0[8], w1[8], wq[8];
-    rv_load(w0, P.ex[9] + (size_t)o * ldw4, ld3, c.lane);
-    rv_load(w1, P.ex[10] + (size_t)o * ldw4, ld3, c.lane);
-    rv_load(wq, P.ex[11] + (size_t)o * ldw4, ld3, c.lane);
-    const float tq0 = wsum(rv_pdot(x0[0], w0, K3, c.lane)) + gld(P.ex[12] + o);
-    const float tq1 = cdq ? wsum(rv_pdot(x1[0], w1, K3, c.lane)) + gld(P.ex[13] + o) : tq0;
-    const float q = wsum(rv_pdot(xq[0], wq, K3, c.lane)) + gld(P.ex[14] + o);
-    const float y = rw + (nd * P.exf[0]) * fminf(tq0, tq1);          // TD3_particles.py:183-189
+    rv_load(w0, P.ex[kW4] + (size_t)o * ldw4, ld3, c.lane);
+    rv_load(w1, P.ex[kW4 + 1] + (size_t)o * ldw4, ld3, c.lane);
+    rv_load(wq, P.ex[kW4 + 2] + (size_t)o * ldw4, ld3, c.lane);
+    const float tq0 = wsum(rv_pdot(x0[0], w0, K3, c.lane)) + gld(P.ex[kB4] + o);
+    const float tq1 = cdq ? wsum(rv_pdot(x1[0], w1, K3, c.lane)) + gld(P.ex[kB4 + 1] + o) : tq0;
+    const float q = wsum(rv_pdot(xq[0], wq, K3, c.lane)) + gld(P.ex[kB4 + 2] + o);
+    const float y = rw + (nd * P.exf[kDiscount]) * fminf(tq0, tq1);          // TD3_particles.py:183-189
     const float d = q - y;
-    const float gq = live ? P.exf[1] * d : 0.f;                       // mse over B*A
+    const float gq = live ? P.exf[kGradScale] * d : 0.f;                       // mse over B*A
     se += live ? d * d : 0.f;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) gu[0][jj] += gq * wq[jj];
     if (c.lane == 0) {
-      gst(P.ex[17] + ((size_t)c.row * 32 + o), gq);
-      gst(P.ex[23] + ((size_t)c.row * 32 + o), q);
-      if (j == 0) gst(P.ex[21] + ((size_t)c.row * 32 + o), y);
+      gst(P.ex[kDZ4] + ((size_t)c.row * 32 + o), gq);
+      gst(P.ex[kQ] + ((size_t)c.row * 32 + o), q);
+      if (j == 0) gst(P.ex[kY] + ((size_t)c.row * 32 + o), y);
     }
   }
   if (c.lane == 0) {
-    gst(P.ex[22] + c.row, se);
+    gst(P.ex[kSqErr] + c.row, se);
     if (NORM) {
-      gst(P.ex[20] + c.row, mq[0]);
-      gst(P.ex[20] + (c.Bp + c.row), sq[0]);
+      gst(P.ex[kStats3] + c.row, mq[0]);
+      gst(P.ex[kStats3] + (c.Bp + c.row), sq[0]);
     }
   }
-  rv_store(P.ex[18] + (size_t)c.row * ld3, ld3, c.lane, gu[0]);
-  if (NORM) rv_store(P.ex[19] + (size_t)c.row * ld3, ld3, c.lane, xq[0]);
+  rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu[0]);
+  if (NORM) rv_store(P.ex[kU3] + (size_t)c.row * ld3, ld3, c.lane, xq[0]);
   ln_bwd_rows<1>(gu, h, g[2], mq, sq, K3, c.lane, NORM);
   rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu[0]);
 }
 
 // -mean over B*nq of Q1(s, pi(s)) (TD3_particles.py:211-212), head + LN3 backward of Q1.
-// ex[0]=H3 ex[1]=gamma3 ex[2]=beta3 ex[3]=W4 ex[4]=b4  out ex[5]=Q [Bp][32], Aout=dZ3
-// exi[0]=K3 exi[1]=ld3 exi[2]=nq exi[3]=ldw4   exf[0]=-1/(B*nq)
+// (operands: actor_loss_p, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_actor_loss_p(const GemmProb& P, const RowCtx& c) {
-  const int K3 = P.exi[0], ld3 = P.exi[1], nq = P.exi[2], ldw4 = P.exi[3];
+  using namespace actor_loss_p;
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3], nq = P.exi[kNq], ldw4 = P.exi[kLdw4];
   float x[1][8], h[1][8], g[8], bb[8], mean[1], rstd[1];
-  rv_load(x[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
   if (NORM) {
-    rv_load(g, P.ex[1], ld3, c.lane);
-    rv_load(bb, P.ex[2], ld3, c.lane);
+    rv_load(g, P.ex[kGamma3], ld3, c.lane);
+    rv_load(bb, P.ex[kBeta3], ld3, c.lane);
   }
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) h[0][jj] = x[0][jj];
   if (NORM) ln_fwd_rows<1>(x, g, bb, K3, c.lane, mean, rstd);
-  const float gq = c.row < P.B ? P.exf[0] : 0.f;
+  const float gq = c.row < P.B ? P.exf[kGradScale] : 0.f;
   float gu[1][8];
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) gu[0][jj] = 0.f;
   for (int o = 0; o < nq; ++o) {
     float w[8];
-    rv_load(w, P.ex[3] + (size_t)o * ldw4, ld3, c.lane);
-    const float q = wsum(rv_pdot(x[0], w, K3, c.lane)) + gld(P.ex[4] + o);
-    if (c.lane == 0) gst(P.ex[5] + ((size_t)c.row * 32 + o), q);
+    rv_load(w, P.ex[kW4] + (size_t)o * ldw4, ld3, c.lane);
+    const float q = wsum(rv_pdot(x[0], w, K3, c.lane)) + gld(P.ex[kB4] + o);
+    if (c.lane == 0) gst(P.ex[kQ] + ((size_t)c.row * 32 + o), q);
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) gu[0][jj] += gq * w[jj];
   }
@@ -1042,32 +947,29 @@ __device__ __forceinline__ void row_actor_loss_p(const GemmProb& P, const RowCtx
 
 // dQ1/da through lnorm1 (the Q input LayerNorm, no ReLU before it), tanh backward (no
 // max_action, TD3_particles.py:68), then the actor head and LN3 backward.
-// ex[0]=dU_in of Q1(s,pi) (grad of the lnorm1 output) ex[1]=X of Q1(s,pi) ex[2]=lnorm1 stats
-// ex[3]=lnorm1 gamma (q1) ex[5]=T (tanh out, [Bp][32]) ex[6]=W4 (actor) ex[7]=H3 (actor)
-// ex[8]=stats3 (actor) ex[9]=gamma3 (actor)   out: ex[10]=dZ4 actor (ld 32) ex[11]=dU3 actor, Aout=dZ3
-// exi[0]=Kin exi[1]=ld_in exi[3]=first action column exi[4]=ad exi[5]=K3 exi[6]=ld3 exi[7]=ldw4
-// exf[0]=max_action scale of the policy output
+// (operands: actor_head_bwd_p, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_actor_head_bwd_p(const GemmProb& P, const RowCtx& c) {
-  const int Kin = P.exi[0], ldin = P.exi[1], acol = P.exi[3], ad = P.exi[4];
-  const int K3 = P.exi[5], ld3 = P.exi[6], ldw4 = P.exi[7];
-  const float ma = P.exf[0];
+  using namespace actor_head_bwd_p;
+  const int Kin = P.exi[kKin], ldin = P.exi[kLdIn], acol = P.exi[kActCol], ad = P.exi[kAd];
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3], ldw4 = P.exi[kLdw4];
+  const float ma = P.exf[kMaxAction];
   float gu[1][8], xr[1][8], gi[8], h3[1][8], g3[8], mi[1], ri[1], mn3[1], rs3[1];
-  rv_load(gu[0], P.ex[0] + (size_t)c.row * ldin, ldin, c.lane);
-  rv_load(xr[0], P.ex[1] + (size_t)c.row * ldin, ldin, c.lane);
-  rv_load(h3[0], P.ex[7] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(gu[0], P.ex[kDUin] + (size_t)c.row * ldin, ldin, c.lane);
+  rv_load(xr[0], P.ex[kXin] + (size_t)c.row * ldin, ldin, c.lane);
+  rv_load(h3[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
   if (NORM) {
-    rv_load(gi, P.ex[3], ldin, c.lane);
-    rv_load(g3, P.ex[9], ld3, c.lane);
-    mi[0] = gld(P.ex[2] + c.row);
-    ri[0] = gld(P.ex[2] + (c.Bp + c.row));
-    mn3[0] = gld(P.ex[8] + c.row);
-    rs3[0] = gld(P.ex[8] + (c.Bp + c.row));
+    rv_load(gi, P.ex[kGammaIn], ldin, c.lane);
+    rv_load(g3, P.ex[kGamma3], ld3, c.lane);
+    mi[0] = gld(P.ex[kStatsIn] + c.row);
+    ri[0] = gld(P.ex[kStatsIn] + (c.Bp + c.row));
+    mn3[0] = gld(P.ex[kStats3] + c.row);
+    rs3[0] = gld(P.ex[kStats3] + (c.Bp + c.row));
   } else {
     mi[0] = mn3[0] = 0.f;
     ri[0] = rs3[0] = 1.f;
   }
-  const float tl = c.lane < ad ? gld(P.ex[5] + ((size_t)c.row * 32 + c.lane)) : 0.f;
+  const float tl = c.lane < ad ? gld(P.ex[kTanh] + ((size_t)c.row * 32 + c.lane)) : 0.f;
   ln_bwd_rows<1, false>(gu, xr, gi, mi, ri, Kin, c.lane, NORM);     // grad of the Q input row
   const bool live = c.row < P.B;
   float gu3[1][8];
@@ -1082,13 +984,13 @@ __device__ __forceinline__ void row_actor_head_bwd_p(const GemmProb& P, const Ro
     const float ga = __shfl(v, (col & 255) >> 2, 64);
     const float t = __shfl(tl, o, 64);
     const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;
-    if (c.lane == 0) gst(P.ex[10] + ((size_t)c.row * 32 + o), gz4);
+    if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + o), gz4);
     float w4[8];
-    rv_load(w4, P.ex[6] + (size_t)o * ldw4, ld3, c.lane);
+    rv_load(w4, P.ex[kW4] + (size_t)o * ldw4, ld3, c.lane);
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4[jj];
   }
-  rv_store(P.ex[11] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
+  rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
   ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);
   rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
 }
@@ -1103,42 +1005,42 @@ constexpr int kRowWaves = TD3_ROW_WAVES;   // waves (rows) per row-kernel workgr
 // dL/dQ_j (LayerNorm backward and relu' are linear in the incoming gradient for fixed forward
 // activations), so the input-grad chain runs on these unit rows while the target path is still
 // computing y; the dW stage scales row r by g_r = 2/B (Q_j,r - y_r) (kRowTargetLoss).
-// ex[0]=H3_j ex[1]=gamma3 ex[2]=beta3 ex[3]=w4 ex[4]=b4
-// out: ex[5]=Q_j ex[6]=U3_j ex[7]=stats3_j ex[8]=dU3_j (unit: w4) Aout=dZ3_j (unit)
-// exi[0]=K3 exi[1]=ld3
+// (operands: unit_loss, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_unit_loss(const GemmProb& P, const RowCtx& c) {
-  asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.ex[5]),
-               "s"(P.ex[6]), "s"(P.ex[7]), "s"(P.ex[8]), "s"(P.exi[0]), "s"(P.exi[1]), "s"(P.Aout), "s"(P.ldao));
-  const int K3 = P.exi[0], ld3 = P.exi[1];
+  using namespace unit_loss;
+  asm volatile("" ::"s"(P.ex[kH3]), "s"(P.ex[kGamma3]), "s"(P.ex[kBeta3]), "s"(P.ex[kW4]), "s"(P.ex[kB4]),
+               "s"(P.ex[kQ]), "s"(P.ex[kU3]), "s"(P.ex[kStats3]), "s"(P.ex[kDU3]), "s"(P.exi[kK3]), "s"(P.exi[kLd3]),
+               "s"(P.Aout), "s"(P.ldao));
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3];
   float x[1][8], h[1][8], g[8], bb[8], w[8], mean[1] = {0.f}, rstd[1] = {1.f};
-  rv_load(x[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
   if (NORM) {
-    rv_load(g, P.ex[1], ld3, c.lane);
-    rv_load(bb, P.ex[2], ld3, c.lane);
+    rv_load(g, P.ex[kGamma3], ld3, c.lane);
+    rv_load(bb, P.ex[kBeta3], ld3, c.lane);
   } else {
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) g[jj] = bb[jj] = 0.f;
   }
-  rv_load(w, P.ex[3], ld3, c.lane);
-  const float b4 = gld(P.ex[4]);
+  rv_load(w, P.ex[kW4], ld3, c.lane);
+  const float b4 = gld(P.ex[kB4]);
   __builtin_amdgcn_sched_barrier(0);     // every load requested before the first use
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) h[0][jj] = x[0][jj];
   if (NORM) ln_fwd_rows<1>(x, g, bb, K3, c.lane, mean, rstd);
   const float q = wsum(rv_pdot(x[0], w, K3, c.lane)) + b4;
   if (c.lane == 0) {
-    gst(P.ex[5] + c.row, q);
+    gst(P.ex[kQ] + c.row, q);
     if (NORM) {
-      gst(P.ex[7] + c.row, mean[0]);
-      gst(P.ex[7] + (c.Bp + c.row), rstd[0]);
+      gst(P.ex[kStats3] + c.row, mean[0]);
+      gst(P.ex[kStats3] + (c.Bp + c.row), rstd[0]);
     }
   }
-  if (NORM) rv_store(P.ex[6] + (size_t)c.row * ld3, ld3, c.lane, x[0]);
+  if (NORM) rv_store(P.ex[kU3] + (size_t)c.row * ld3, ld3, c.lane, x[0]);
   float gu[1][8];
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) gu[0][jj] = w[jj];
-  rv_store(P.ex[8] + (size_t)c.row * ld3, ld3, c.lane, gu[0]);
+  rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu[0]);
   ln_bwd_rows<1>(gu, h, g, mean, rstd, K3, c.lane, NORM);
   rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu[0]);
 }
@@ -1147,32 +1049,31 @@ __device__ __forceinline__ void row_unit_loss(const GemmProb& P, const RowCtx& c
 // y = r + not_done * discount * min(Q1'(s',a'), Q2'(s',a')) (TD3_featured.py:140-142) and for both
 // online critics g_j = 2/B (Q_j - y) (F.mse_loss backward, :148): the head's dZ4_j and the row
 // scale of Q_j's unit backward in the dW stage; the squared errors for the loss read-back.
-// ex[0..1]=H3 of target q1 / q2  ex[2..3]=gamma3  ex[4..5]=beta3  ex[6..7]=w4  ex[8..9]=b4
-// ex[10]=reward ex[11]=not_done ex[12..13]=Q_1 / Q_2 (kRowUnitLoss)
-// out: ex[14]=y ex[15..16]=dZ4 of q1 / q2 (ld 32) ex[17]=sqerr [2][Bp] ex[18..19]=g of q1 / q2 [Bp]
-// exi[0]=K3 exi[1]=ld3   exf[0]=discount exf[1]=2/B
+// (operands: target_loss, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_target_loss(const GemmProb& P, const RowCtx& c) {
-  asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.ex[5]),
-               "s"(P.ex[6]), "s"(P.ex[7]), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.ex[10]), "s"(P.ex[11]),
-               "s"(P.ex[12]), "s"(P.ex[13]), "s"(P.exi[0]), "s"(P.exi[1]));
-  asm volatile("" ::"s"(P.ex[14]), "s"(P.ex[15]), "s"(P.ex[16]), "s"(P.ex[17]), "s"(P.ex[18]), "s"(P.ex[19]),
-               "s"(P.exf[0]), "s"(P.exf[1]), "s"(P.B));
-  const int K3 = P.exi[0], ld3 = P.exi[1];
+  using namespace target_loss;
+  asm volatile("" ::"s"(P.ex[kH3]), "s"(P.ex[kH3 + 1]), "s"(P.ex[kGamma3]), "s"(P.ex[kGamma3 + 1]), "s"(P.ex[kBeta3]),
+               "s"(P.ex[kBeta3 + 1]), "s"(P.ex[kW4]), "s"(P.ex[kW4 + 1]), "s"(P.ex[kB4]), "s"(P.ex[kB4 + 1]),
+               "s"(P.ex[kReward]), "s"(P.ex[kNotDone]), "s"(P.ex[kQ]), "s"(P.ex[kQ + 1]), "s"(P.exi[kK3]),
+               "s"(P.exi[kLd3]));
+  asm volatile("" ::"s"(P.ex[kY]), "s"(P.ex[kDZ4]), "s"(P.ex[kDZ4 + 1]), "s"(P.ex[kSqErr]), "s"(P.ex[kG]),
+               "s"(P.ex[kG + 1]), "s"(P.exf[kDiscount]), "s"(P.exf[kGradScale]), "s"(P.B));
+  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3];
   float x0[1][8], x1[1][8], g[2][8], bb[2][8], w[2][8];
-  rv_load(x0[0], P.ex[0] + (size_t)c.row * ld3, ld3, c.lane);
-  rv_load(x1[0], P.ex[1] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x0[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
+  rv_load(x1[0], P.ex[kH3 + 1] + (size_t)c.row * ld3, ld3, c.lane);
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     if (NORM) {
-      rv_load(g[n], P.ex[2 + n], ld3, c.lane);
-      rv_load(bb[n], P.ex[4 + n], ld3, c.lane);
+      rv_load(g[n], P.ex[kGamma3 + n], ld3, c.lane);
+      rv_load(bb[n], P.ex[kBeta3 + n], ld3, c.lane);
     }
-    rv_load(w[n], P.ex[6 + n], ld3, c.lane);
+    rv_load(w[n], P.ex[kW4 + n], ld3, c.lane);
   }
-  const float b40 = gld(P.ex[8]), b41 = gld(P.ex[9]);
-  const float rw = gld(P.ex[10] + c.row), nd = gld(P.ex[11] + c.row);
-  const float q1 = gld(P.ex[12] + c.row), q2 = gld(P.ex[13] + c.row);
+  const float b40 = gld(P.ex[kB4]), b41 = gld(P.ex[kB4 + 1]);
+  const float rw = gld(P.ex[kReward] + c.row), nd = gld(P.ex[kNotDone] + c.row);
+  const float q1 = gld(P.ex[kQ] + c.row), q2 = gld(P.ex[kQ + 1] + c.row);
   __builtin_amdgcn_sched_barrier(0);     // every load requested before the first use
   float m0[1], s0[1], m1[1], s1[1];
   if (NORM) {
@@ -1182,36 +1083,38 @@ __device__ __forceinline__ void row_target_loss(const GemmProb& P, const RowCtx&
   const float d0 = rv_pdot(x0[0], w[0], K3, c.lane);
   const float d1 = rv_pdot(x1[0], w[1], K3, c.lane);
   const float tq0 = wsum(d0) + b40, tq1 = wsum(d1) + b41;
-  const float y = rw + (nd * P.exf[0]) * fminf(tq0, tq1);                  // :141-142
+  const float y = rw + (nd * P.exf[kDiscount]) * fminf(tq0, tq1);                  // :141-142
   const bool live = c.row < P.B;
   const float e1 = q1 - y, e2 = q2 - y;
-  const float g1 = live ? P.exf[1] * e1 : 0.f, g2 = live ? P.exf[1] * e2 : 0.f;   // mse_loss bwd (:148)
+  // mse_loss bwd (:148)
+  const float g1 = live ? P.exf[kGradScale] * e1 : 0.f, g2 = live ? P.exf[kGradScale] * e2 : 0.f;
   if (c.lane == 0) {
-    gst(P.ex[14] + c.row, y);
-    gst(P.ex[15] + ((size_t)c.row * 32), g1);
-    gst(P.ex[16] + ((size_t)c.row * 32), g2);
-    gst(P.ex[17] + c.row, live ? e1 * e1 : 0.f);
-    gst(P.ex[17] + (c.Bp + c.row), live ? e2 * e2 : 0.f);
-    gst(P.ex[18] + c.row, g1);
-    gst(P.ex[19] + c.row, g2);
+    gst(P.ex[kY] + c.row, y);
+    gst(P.ex[kDZ4] + ((size_t)c.row * 32), g1);
+    gst(P.ex[kDZ4 + 1] + ((size_t)c.row * 32), g2);
+    gst(P.ex[kSqErr] + c.row, live ? e1 * e1 : 0.f);
+    gst(P.ex[kSqErr] + (c.Bp + c.row), live ? e2 * e2 : 0.f);
+    gst(P.ex[kG] + c.row, g1);
+    gst(P.ex[kG + 1] + c.row, g2);
   }
 }
 
 // ---- dZ = relu'(LN_bwd(dU)) of full rows (kRowLnBwd): lnbwd_rows_kernel's row as a row kind,
 // so it can share a launch with another row stage.
-// ex[0]=dU ex[1]=H ex[2]=stats ex[3]=gamma  out: ex[4]=dZ   exi[0]=ld exi[1]=K
+// (operands: ln_bwd, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_lnbwd(const GemmProb& P, const RowCtx& c) {
-  asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.exi[0]),
-               "s"(P.exi[1]));
-  const int ld = P.exi[0];
+  using namespace ln_bwd;
+  asm volatile("" ::"s"(P.ex[kDU]), "s"(P.ex[kH]), "s"(P.ex[kStats]), "s"(P.ex[kGamma]), "s"(P.ex[kDZ]),
+               "s"(P.exi[kLd]), "s"(P.exi[kK]));
+  const int ld = P.exi[kLd];
   float gu[1][8], h[1][8], g[8], mean[1], rstd[1];
   float4 qg[2], qu[2], qh[2];
-  if constexpr (NORM) rv_load_raw(qg, P.ex[3], ld, c.lane);
-  rv_load_raw(qu, P.ex[0] + (size_t)c.row * ld, ld, c.lane);
-  rv_load_raw(qh, P.ex[1] + (size_t)c.row * ld, ld, c.lane);
-  mean[0] = NORM ? gld(P.ex[2] + c.row) : 0.f;
-  rstd[0] = NORM ? gld(P.ex[2] + (c.Bp + c.row)) : 1.f;
+  if constexpr (NORM) rv_load_raw(qg, P.ex[kGamma], ld, c.lane);
+  rv_load_raw(qu, P.ex[kDU] + (size_t)c.row * ld, ld, c.lane);
+  rv_load_raw(qh, P.ex[kH] + (size_t)c.row * ld, ld, c.lane);
+  mean[0] = NORM ? gld(P.ex[kStats] + c.row) : 0.f;
+  rstd[0] = NORM ? gld(P.ex[kStats] + (c.Bp + c.row)) : 1.f;
   __builtin_amdgcn_sched_barrier(0);     // every load requested before the first use
   if constexpr (NORM) rv_from_raw(g, qg, ld, c.lane);
   else {
@@ -1220,16 +1123,14 @@ __device__ __forceinline__ void row_lnbwd(const GemmProb& P, const RowCtx& c) {
   }
   rv_from_raw(gu[0], qu, ld, c.lane);
   rv_from_raw(h[0], qh, ld, c.lane);
-  if constexpr (NORM) ln_bwd_rows_pk<1>(gu, h, g, mean, rstd, 1.0f / (float)P.exi[1]);
-  else ln_bwd_rows<1>(gu, h, g, mean, rstd, P.exi[1], c.lane, 0);
-  rv_store(P.ex[4] + (size_t)c.row * ld, ld, c.lane, gu[0]);
+  if constexpr (NORM) ln_bwd_rows_pk<1>(gu, h, g, mean, rstd, 1.0f / (float)P.exi[kK]);
+  else ln_bwd_rows<1>(gu, h, g, mean, rstd, P.exi[kK], c.lane, 0);
+  rv_store(P.ex[kDZ] + (size_t)c.row * ld, ld, c.lane, gu[0]);
 }
 
 template <int KIND, bool NORM, int RW>
 __device__ __forceinline__ void row_dispatch(const GemmProb& P, const RowCtx& c) {
   if constexpr (KIND == kRowPolicyHead) row_policy_head<NORM, RW>(P, c);
-  else if constexpr (KIND == kRowCriticLoss) row_critic_loss<NORM>(P, c);
-  else if constexpr (KIND == kRowActorLoss) row_actor_loss<NORM>(P, c);
   else if constexpr (KIND == kRowActorHeadBwd) row_actor_head_bwd<NORM, RW>(P, c);
   else if constexpr (KIND == kRowCriticLossP) row_critic_loss_p<NORM>(P, c);
   else if constexpr (KIND == kRowActorLossP) row_actor_loss_p<NORM>(P, c);
@@ -1276,7 +1177,7 @@ __global__ __launch_bounds__(64 * RW) void row_kernel2(int Bp, int n1, GemmTable
 
 // The k-quad stride of a MODE 0 weight image (GemmProb::wsk; 0: row-major)
 __device__ __forceinline__ int w_sk(int wsk) { return wsk ? wsk : 4; }
-// W0 of the fused layer-0 stages (ex[8]): row stride and k-quad stride (GemmProb::w0sk)
+// W0 of the fused layer-0 stages (ring_l0::kW0): row stride and k-quad stride (GemmProb::w0sk)
 __device__ __forceinline__ int w0_sn(int w0sk) { return w0sk ? 4 : 32; }
 __device__ __forceinline__ int w0_sk(int w0sk) { return w0sk ? w0sk : 4; }
 
@@ -1358,6 +1259,7 @@ __device__ __forceinline__ int xcd_tile(int nb) {
 template <int MODE, int WN, int PRO, int NW = kNW>
 __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, int tb3, int Bp, const GemmTable& tab,
                                           Counters* bump, int bump_actor, float* smem) {
+  using namespace ring_l0;
   constexpr int RT = wn_rt(WN);                // 32-row tiles of the workgroup (kWn4x2: 2)
   constexpr int RPW = 32 * RT / NW;            // prologue rows per wave
   static_assert(NW == kNW || (PRO != kProL0 && PRO != kProL0G), "fused layer 0 runs kNW waves");
@@ -1385,27 +1287,29 @@ __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, in
     // statement is a use, i.e. a wait: two statements were two dependent round trips); the rest
     // are batched behind the operand requests (l0_late_fields)
     if constexpr (PRO == kProL0G)
-      asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.exi[5]), "s"(P.exi[6]), "s"(P.W),
-                   "s"(P.ldw), "s"(P.Kp), "s"(P.lng), "s"(P.lnb), "s"(P.bias), "s"(P.Nout), "s"(P.tile_begin),
-                   "s"(P.norm), "s"(P.B), "s"(tab.rs.data), "s"(tab.rs.rec), "s"(tab.rs.d_size), "s"(tab.rs.seed),
-                   "s"(tab.rs.ctr), "s"(P.exi[0]), "s"(P.exi[1]), "s"(P.wsk), "s"(P.w0sk));
+      asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[kW0]), "s"(P.ex[kB0]), "s"(P.exi[kN0p]), "s"(P.exi[kK0]),
+                   "s"(P.W), "s"(P.ldw), "s"(P.Kp), "s"(P.lng), "s"(P.lnb), "s"(P.bias), "s"(P.Nout),
+                   "s"(P.tile_begin), "s"(P.norm), "s"(P.B), "s"(tab.rs.data), "s"(tab.rs.rec), "s"(tab.rs.d_size),
+                   "s"(tab.rs.seed), "s"(tab.rs.ctr), "s"(P.exi[kRecOff]), "s"(P.exi[kRecOffRw]), "s"(P.wsk),
+                   "s"(P.w0sk));
     else
-      asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.exi[5]), "s"(P.exi[6]), "s"(P.W),
-                   "s"(P.ldw), "s"(P.Kp), "s"(P.lng), "s"(P.lnb), "s"(P.bias), "s"(P.Nout), "s"(P.tile_begin),
-                   "s"(P.norm), "s"(P.B), "s"(P.wsk), "s"(P.w0sk));
+      asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[kW0]), "s"(P.ex[kB0]), "s"(P.exi[kN0p]), "s"(P.exi[kK0]),
+                   "s"(P.W), "s"(P.ldw), "s"(P.Kp), "s"(P.lng), "s"(P.lnb), "s"(P.bias), "s"(P.Nout),
+                   "s"(P.tile_begin), "s"(P.norm), "s"(P.B), "s"(P.wsk), "s"(P.w0sk));
   } else {
     if constexpr (PRO == kProHeadBwd)      // one batch with the head operands (a second asm would be a
-      asm volatile("" ::"s"(P.A), "s"(P.lng), "s"(P.lnb), "s"(P.W), "s"(P.C), "s"(P.lda), "s"(P.Kreal),
-                   "s"(P.Kp), "s"(P.ldw), "s"(P.Nout), "s"(P.ldc), "s"(P.ntiles), "s"(P.tile_begin),
-                   "s"(P.norm), "s"(P.B), "s"(P.ex[3]), "s"(P.ex[4]), "s"(P.ex[5]), "s"(P.exf[0]));
+      asm volatile("" ::"s"(P.A), "s"(P.lng), "s"(P.lnb), "s"(P.W), "s"(P.C), "s"(P.lda), "s"(P.Kreal), "s"(P.Kp),
+                   "s"(P.ldw), "s"(P.Nout), "s"(P.ldc), "s"(P.ntiles), "s"(P.tile_begin), "s"(P.norm), "s"(P.B),
+                   "s"(P.ex[head_bwd_pro::kW4]), "s"(P.ex[head_bwd_pro::kB4]), "s"(P.ex[head_bwd_pro::kQ]),
+                   "s"(P.exf[head_bwd_pro::kGradScale]));
     else                                   // second dependent kernel-argument round trip)
       asm volatile("" ::"s"(P.A), "s"(P.lng), "s"(P.lnb), "s"(P.H), "s"(P.stats), "s"(P.Aout), "s"(P.W), "s"(P.bias),
                    "s"(P.C), "s"(P.lda), "s"(P.Kreal), "s"(P.Kp), "s"(P.ldh), "s"(P.ldao), "s"(P.ldw), "s"(P.Nout),
                    "s"(P.ldc), "s"(P.relu), "s"(P.ntiles), "s"(P.tile_begin), "s"(P.norm), "s"(P.B), "s"(P.wsk));
     if constexpr (PRO == kProGather)
-      asm volatile("" ::"s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.exi[0]), "s"(P.exi[1]), "s"(P.exi[3]),
-                   "s"(tab.rs.data), "s"(tab.rs.rec), "s"(tab.rs.d_size), "s"(tab.rs.idx_out), "s"(tab.rs.seed),
-                   "s"(tab.rs.ctr));
+      asm volatile("" ::"s"(P.ex[kRowCopy2]), "s"(P.ex[kReward]), "s"(P.ex[kNotDone]), "s"(P.exi[kRecOff]),
+                   "s"(P.exi[kRecOffRw]), "s"(P.exi[kLdRowCopy2]), "s"(tab.rs.data), "s"(tab.rs.rec),
+                   "s"(tab.rs.d_size), "s"(tab.rs.idx_out), "s"(tab.rs.seed), "s"(tab.rs.ctr));
   }
   const int mtiles = (Bp >> 5) / RT;
   const int t = b - P.tile_begin;
@@ -1444,14 +1348,14 @@ __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, in
     const int sn0 = w0_sn(P.w0sk), sk0 = w0_sk(P.w0sk);
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
-      const int tile = min(wave + kNW * ct, (P.exi[5] >> 5) - 1);
-      const float* wp = P.ex[8] + (size_t)(tile * 32 + i) * sn0 + (size_t)(koff >> 2) * sk0;
+      const int tile = min(wave + kNW * ct, (P.exi[kN0p] >> 5) - 1);
+      const float* wp = P.ex[kW0] + (size_t)(tile * 32 + i) * sn0 + (size_t)(koff >> 2) * sk0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 v = gld4(wp + (size_t)q * sk0);
         w0[ct][4 * q + 0] = v.x; w0[ct][4 * q + 1] = v.y; w0[ct][4 * q + 2] = v.z; w0[ct][4 * q + 3] = v.w;
       }
-      b0v[ct] = gld(P.ex[9] + tile * 32 + i);
+      b0v[ct] = gld(P.ex[kB0] + tile * 32 + i);
     }
   }
   float lg[8], lb[8];                          // kL0: LayerNorm-0 gamma / beta
@@ -1471,9 +1375,9 @@ __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, in
   }
 
   if constexpr (kL0)         // l0_late_fields: requested behind the operand loads (waited for in their shadow)
-    asm volatile("" ::"s"(P.ex[10]), "s"(P.Aout), "s"(P.ldao), "s"(P.stats), "s"(P.Kreal), "s"(P.C), "s"(P.ldc),
-                 "s"(P.relu), "s"(P.ntiles), "s"(P.ex[0]), "s"(P.ex[1]), "s"(P.ex[2]), "s"(P.ex[3]), "s"(P.exi[3]),
-                 "s"(P.exi[8]), "s"(tab.rs.idx_out));
+    asm volatile("" ::"s"(P.ex[kH0]), "s"(P.Aout), "s"(P.ldao), "s"(P.stats), "s"(P.Kreal), "s"(P.C), "s"(P.ldc),
+                 "s"(P.relu), "s"(P.ntiles), "s"(P.ex[kRowCopy2]), "s"(P.ex[kReward]), "s"(P.ex[kNotDone]),
+                 "s"(P.ex[kRowCopy]), "s"(P.exi[kLdRowCopy2]), "s"(P.exi[kLdRowCopy]), "s"(tab.rs.idx_out));
   TL_MARK(5);
   // WN >= 2 waves own more chunks than kCh: the next two are requested right behind the A rows
   // (in flight during the LayerNorm, not queued ahead of it), the rest stream in the MFMA loop
@@ -1653,13 +1557,13 @@ __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, in
     }
   }
   // a separate layer-0 forward stage of the actor phase (td3.hip W1aT): the workgroups of column
-  // tile nt also write its weight rows' columns [exi[10], exi[10] + exi[11]), transposed, for
+  // tile nt also write its weight rows' columns [kTCol, kTCol + kTN), transposed, for
   // actor_head_bwd -- row n0 + r by row tile r % mtiles (done by row tile 0 alone, the copy was
   // that workgroup's tail: AF_fwd0 +0.9 us)
   if constexpr (MODE == 0 && PRO == kProCopy) {
-    float* tc = P.ex[12];
+    float* tc = P.ex[kTCopy];
     if (tc) {
-      const int tcol = P.exi[10], tn = P.exi[11];
+      const int tcol = P.exi[kTCol], tn = P.exi[kTN];
       for (int e = threadIdx.x; e < OUTW * tn; e += NT) {
         const int r = e / tn, o = e % tn, n = n0 + r;
         if (r % mtiles == mt && n < P.Nout) gst(tc + ((size_t)o * P.Nout + n), gld(P.W + ((size_t)n * P.ldw + (size_t)((tcol + o) >> 2) * w_sk(P.wsk) + ((tcol + o) & 3))));
@@ -1751,6 +1655,7 @@ constexpr int kR16XS = 36;      // LDS row stride of the staged 16 input rows
 template <int NCT, int WK, bool GATHER>
 __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob, int tb1, int tb2, int tb3, int Bp,
                                                               GemmTable tab, Counters* bump, int bump_actor) {
+  using namespace ring_l0;
   constexpr int NW = NCT * WK, NT = 64 * NW, OUTW = 16 * NCT;
   static_assert(NW >= 8 && NW <= 16 && NT % OUTW == 0, "l0r16: 8 .. 16 waves, whole output rows per pass");
   extern __shared__ float4 smem4[];
@@ -1765,12 +1670,12 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
   pi = __builtin_amdgcn_readfirstlane(pi);
   const GemmProb& P = tab.p[pi];
   if constexpr (GATHER)
-    asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.exi[5]), "s"(P.exi[6]), "s"(P.W),
+    asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[kW0]), "s"(P.ex[kB0]), "s"(P.exi[kN0p]), "s"(P.exi[kK0]), "s"(P.W),
                  "s"(P.ldw), "s"(P.Kp), "s"(P.lng), "s"(P.lnb), "s"(P.bias), "s"(P.Nout), "s"(P.tile_begin),
                  "s"(P.norm), "s"(P.B), "s"(tab.rs.data), "s"(tab.rs.rec), "s"(tab.rs.d_size), "s"(tab.rs.seed),
-                 "s"(tab.rs.ctr), "s"(P.exi[0]), "s"(P.exi[1]), "s"(P.wsk), "s"(P.w0sk));
+                 "s"(tab.rs.ctr), "s"(P.exi[kRecOff]), "s"(P.exi[kRecOffRw]), "s"(P.wsk), "s"(P.w0sk));
   else
-    asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[8]), "s"(P.ex[9]), "s"(P.exi[5]), "s"(P.exi[6]), "s"(P.W),
+    asm volatile("" ::"s"(P.A), "s"(P.lda), "s"(P.ex[kW0]), "s"(P.ex[kB0]), "s"(P.exi[kN0p]), "s"(P.exi[kK0]), "s"(P.W),
                  "s"(P.ldw), "s"(P.Kp), "s"(P.lng), "s"(P.lnb), "s"(P.bias), "s"(P.Nout), "s"(P.tile_begin),
                  "s"(P.norm), "s"(P.B), "s"(P.wsk), "s"(P.w0sk));
   const int mtiles = Bp >> 4;
@@ -1785,7 +1690,7 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
   float* red = h0s + 16 * S;                    // [NW][16][17]: layer-1 K-split partials
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int j16 = lane & 15, g = lane >> 4;
-  const int K0 = P.exi[6], N0p = P.exi[5];
+  const int K0 = P.exi[kK0], N0p = P.exi[kN0p];
   const bool t0 = nt == 0;
   // ---- 1. input rows (loads first: the record reads are the latency-critical ones)
   const int xrow = (threadIdx.x >> 5) & 15, xcol = threadIdx.x & 31;
@@ -1799,8 +1704,8 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
     idx = grow_x < P.B ? (int64_t)philox_index(tab.rs.seed, step, (uint32_t)grow_x, n) : -1;
     __builtin_amdgcn_sched_barrier(0);
     const float* rec = tab.rs.data + (size_t)(idx >= 0 ? idx : 0) * tab.rs.rec;
-    xv = gld(rec + P.exi[0] + (xcol < K0 ? xcol : 0));
-    rw = t0 ? gld(rec + P.exi[1] + (xcol & 1)) : 0.f;
+    xv = gld(rec + P.exi[kRecOff] + (xcol < K0 ? xcol : 0));
+    rw = t0 ? gld(rec + P.exi[kRecOffRw] + (xcol & 1)) : 0.f;
   } else {
     xv = gld(P.A + (size_t)grow_x * P.lda + xcol);   // input rows are >= 32 wide (zero pads)
   }
@@ -1814,11 +1719,11 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
 #pragma unroll
   for (int q = 0; q < kQ0; ++q) {
     const int tau = min(wave + NW * q, n0t - 1);
-    const float* wp = P.ex[8] + (size_t)(tau * 16 + j16) * w0_sn(P.w0sk) + (size_t)(2 * g) * w0_sk(P.w0sk);
+    const float* wp = P.ex[kW0] + (size_t)(tau * 16 + j16) * w0_sn(P.w0sk) + (size_t)(2 * g) * w0_sk(P.w0sk);
     const float4 u = gld4(wp), v = gld4(wp + w0_sk(P.w0sk));
     w0[q][0] = u.x; w0[q][1] = u.y; w0[q][2] = u.z; w0[q][3] = u.w;
     w0[q][4] = v.x; w0[q][5] = v.y; w0[q][6] = v.z; w0[q][7] = v.w;
-    b0v[q] = gld(P.ex[9] + tau * 16 + j16);
+    b0v[q] = gld(P.ex[kB0] + tau * 16 + j16);
   }
   float lg[8], lb[8];
   if (P.norm) {
@@ -1858,8 +1763,8 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
     if constexpr (GATHER) {
       if (t0) {
         if (valid) {
-          if (P.ex[3]) gst(P.ex[3] + (size_t)grow_x * P.exi[8] + xcol, x);
-          if (P.ex[0]) gst(P.ex[0] + (size_t)grow_x * P.exi[3] + xcol, x);
+          if (P.ex[kRowCopy]) gst(P.ex[kRowCopy] + (size_t)grow_x * P.exi[kLdRowCopy] + xcol, x);
+          if (P.ex[kRowCopy2]) gst(P.ex[kRowCopy2] + (size_t)grow_x * P.exi[kLdRowCopy2] + xcol, x);
         }
         if (xcol < 2 && rw_ptr(P, xcol)) gst(rw_ptr(P, xcol) + grow_x, idx >= 0 ? rw : 0.f);
         if (pi == 0 && tab.rs.idx_out && xcol == 0 && grow_x < P.B) tab.rs.idx_out[grow_x] = idx;
@@ -1877,7 +1782,7 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
     __builtin_amdgcn_sched_barrier(0);
   }
   // ---- 2. layer 0 on MFMA: A = the staged rows (lane (j16, g) supplies x[j16][8g + s])
-  const bool keep = P.ex[10] && P.norm;
+  const bool keep = P.ex[kH0] && P.norm;
   {
     const float4 x0 = *reinterpret_cast<const float4*>(xs + j16 * kR16XS + 8 * g);
     const float4 x1 = *reinterpret_cast<const float4*>(xs + j16 * kR16XS + 8 * g + 4);
@@ -1960,7 +1865,7 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
   // H0 / U0 rows of the tile, each n-tile workgroup its slice of the columns (after the MFMA loop:
   // in the prologue they queued ahead of the weight stream)
   {
-    float* H0 = P.ex[10];
+    float* H0 = P.ex[kH0];
     float* U0 = P.norm ? P.Aout : nullptr;
     const float* hsrc = P.norm ? h0s : abuf;
     if (H0 || U0) {
@@ -1969,7 +1874,7 @@ __global__ __launch_bounds__(64 * NCT * WK) void l0r16_kernel(int nb, int nprob,
       for (int e = threadIdx.x; e < 16 * per; e += NT) {
         const int row = e / per, q4 = 4 * (q0 + e % per);
         const size_t grow = (size_t)(m0 + row);
-        if (H0) gst4(H0 + grow * P.exi[5] + q4, *reinterpret_cast<const float4*>(hsrc + row * S + q4));
+        if (H0) gst4(H0 + grow * P.exi[kN0p] + q4, *reinterpret_cast<const float4*>(hsrc + row * S + q4));
         if (U0) gst4(U0 + grow * P.ldao + q4, *reinterpret_cast<const float4*>(abuf + row * S + q4));
       }
     }
@@ -3681,12 +3586,13 @@ int launch_l0r16(int nct, int wk, int gather, const GemmTable& t, int nblocks, i
     set_error("launch_l0r16: Bp %d is not a multiple of 16", Bp);
     return -1;
   }
-  for (int k = 0; k < t.nprob; ++k)
-    if (t.p[k].Kp > 512 || t.p[k].exi[6] < 1 || t.p[k].exi[6] > 32 || t.p[k].exi[5] > 512 || t.p[k].exi[5] != t.p[k].Kp) {
-      set_error("launch_l0r16: unsupported layer-0/1 shape (K0 %d, N0p %d, Kp %d)", t.p[k].exi[6], t.p[k].exi[5],
-                t.p[k].Kp);
+  for (int k = 0; k < t.nprob; ++k) {
+    const int K0 = t.p[k].exi[ring_l0::kK0], N0p = t.p[k].exi[ring_l0::kN0p], Kp = t.p[k].Kp;
+    if (Kp > 512 || K0 < 1 || K0 > 32 || N0p > 512 || N0p != Kp) {
+      set_error("launch_l0r16: unsupported layer-0/1 shape (K0 %d, N0p %d, Kp %d)", K0, N0p, Kp);
       return -1;
     }
+  }
   const int padded = (nblocks + 7) & ~7;
   const int tb1 = t.nprob > 1 ? t.p[1].tile_begin : nblocks, tb2 = t.nprob > 2 ? t.p[2].tile_begin : nblocks;
   const int tb3 = t.nprob > 3 ? t.p[3].tile_begin : nblocks;
@@ -3729,12 +3635,14 @@ static int wide_head_bytes(int kind, const GemmProb& p) {
   const auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   size_t n = 0;
   if (kind == kRowPolicyHead) {
-    const int ad = p.exi[5], ldw4 = p.exi[2];
-    if (ad <= kHeadRegs || ldw4 % 4 || !al16(p.ex[3])) return 0;
+    const int ad = p.exi[policy_head::kAd], ldw4 = p.exi[policy_head::kLdw4];
+    if (ad <= kHeadRegs || ldw4 % 4 || !al16(p.ex[policy_head::kW4])) return 0;
     n = (size_t)ad * ldw4;
   } else if (kind == kRowActorHeadBwd) {
-    const int ad = p.exi[4], ldw4 = p.exi[7], ld1 = p.exi[8];
-    if (ad <= kHeadRegs || !p.ex[12] || ld1 % 4 || ldw4 % 4 || !al16(p.ex[12]) || !al16(p.ex[6])) return 0;
+    namespace ab = actor_head_bwd;
+    const int ad = p.exi[ab::kAd], ldw4 = p.exi[ab::kLdw4], ld1 = p.exi[ab::kLdW1T];
+    if (ad <= kHeadRegs || !p.ex[ab::kW1T] || ld1 % 4 || ldw4 % 4 || !al16(p.ex[ab::kW1T]) || !al16(p.ex[ab::kW4]))
+      return 0;
     n = (size_t)ad * (ld1 + ldw4);
   }
   return n * 4 <= (size_t)kWideStage * 64 * kWideRows * 16 ? (int)(n * 4) : 0;
@@ -3756,7 +3664,7 @@ static int mark_wide(GemmTable& d, int k1, int k2, int n1) {
 }
 
 template <bool NORM>
-static void launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) {
+static int launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) {
   const dim3 grid(Bp / kRowWaves, d0.nprob);
   GemmTable d = d0;
   const int lds = mark_wide(d, kind, kind, d.nprob);
@@ -3766,8 +3674,6 @@ static void launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) 
       if (lds) hipLaunchKernelGGL((row_kernel<kRowPolicyHead, NORM, kWideRows>), wgrid, wblock, lds, s, Bp, d);
       else hipLaunchKernelGGL((row_kernel<kRowPolicyHead, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d);
       break;
-    case kRowCriticLoss: hipLaunchKernelGGL((row_kernel<kRowCriticLoss, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d); break;
-    case kRowActorLoss: hipLaunchKernelGGL((row_kernel<kRowActorLoss, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d); break;
     case kRowActorHeadBwd:
       if (lds) hipLaunchKernelGGL((row_kernel<kRowActorHeadBwd, NORM, kWideRows>), wgrid, wblock, lds, s, Bp, d);
       else hipLaunchKernelGGL((row_kernel<kRowActorHeadBwd, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d);
@@ -3779,19 +3685,18 @@ static void launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) 
     case kRowActorHeadBwdP:
       hipLaunchKernelGGL((row_kernel<kRowActorHeadBwdP, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d);
       break;
-    default: break;
+    default:   // the kinds of launch_rows2 only, and the retired values 1 and 2
+      set_error("internal: unknown row kernel %d", kind);
+      return -1;
   }
+  return 0;
 }
 
 // norm is a template parameter of the row kernels: with it a runtime flag, every LayerNorm operand
 // load sat in its own basic block and the scheduler issued the row's loads in ~6 dependent rounds.
 int launch_rows(int kind, const GemmTable& d, int Bp, hipStream_t s) {
-  if (kind < kRowPolicyHead || kind > kRowActorHeadBwdP) {
-    set_error("internal: unknown row kernel %d", kind);
-    return -1;
-  }
-  if (d.p[0].norm) launch_rows_t<true>(kind, d, Bp, s);
-  else launch_rows_t<false>(kind, d, Bp, s);
+  const int rc = d.p[0].norm ? launch_rows_t<true>(kind, d, Bp, s) : launch_rows_t<false>(kind, d, Bp, s);
+  if (rc) return rc;
   TD3_HIP(hipGetLastError());
   return 0;
 }

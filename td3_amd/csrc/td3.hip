@@ -455,7 +455,7 @@ struct FwdItem {
   const NetL* net; const float* P; EvalB* e; bool store_u; bool stats;
   int ring_src = -1;      // layer 0 read from the replay ring (kProGather): record offset of the input
   // separate layer-0 stage only: columns [tcol, tcol + tn) of the layer-0 weight, transposed into
-  // tcopy [tn][Np0] by the stage's first row tile (GemmProb ex[12] / exi[10] / exi[11])
+  // tcopy [tn][Np0] by the stage's first row tile
   float* tcopy = nullptr;
   int tcol = 0, tn = 0;
 };
@@ -463,12 +463,16 @@ struct BwdItem { const NetL* net; const float* P; EvalB* e; bool store_dz; };
 
 // Algorithmic bytes of a GEMM stage's problems: each weight once (and layer 0's for the fused
 // layer-0 stages), the batch rows of A once, the output rows once (real widths, B real rows).
-static double gemm_bytes(const GemmProb* p, int n) {
+static double gemm_bytes(const GemmProb* p, int n, int pro) {
+  const bool l0 = pro == kProL0 || pro == kProL0G;
   double b = 0;
   for (int i = 0; i < n; ++i) {
     const GemmProb& q = p[i];
     b += 4.0 * ((double)q.Nout * q.Kreal + (double)q.B * q.Kreal + (double)q.B * q.Nout);
-    if (q.exi[6] > 0 && q.exi[5] > 0) b += 4.0 * ((double)q.exi[5] * q.exi[6] + (double)q.B * q.exi[6]);
+    if (l0) {
+      const int N0p = q.exi[ring_l0::kN0p], K0 = q.exi[ring_l0::kK0];
+      b += 4.0 * ((double)N0p * K0 + (double)q.B * K0);
+    }
   }
   return b;
 }
@@ -497,14 +501,14 @@ static int push_gemm_stage(td3_handle* h, std::vector<void*>& owned, std::vector
                     return launch_gemm(mode, wn, pro, tt, blocks, Bp, lds, bump, bump_actor, s);
                   },
                   flops, kname});
-    st.back().bytes = gemm_bytes(t.p, t.nprob);
+    st.back().bytes = gemm_bytes(t.p, t.nprob, pro);
     return 0;
   }
   st.push_back({name,
                 [=](hipStream_t s) { return launch_gemm(mode, wn, pro, t, blocks, Bp, lds, bump, bump_actor, s); },
                 flops, kname});
   st.back().gemm = std::make_shared<GemmLaunch>(GemmLaunch{mode, wn, pro, t, blocks, Bp, lds, bump == nullptr});
-  st.back().bytes = gemm_bytes(t.p, t.nprob);
+  st.back().bytes = gemm_bytes(t.p, t.nprob, pro);
   return 0;
 }
 
@@ -837,43 +841,37 @@ static int add_fwd_stages(td3_handle* h, std::vector<void*>& owned, std::vector<
         }
       }
       if (l == 0 && !l0 && !gather && !lnin && it.tcopy) {
-        p.ex[12] = it.tcopy;
-        p.exi[10] = it.tcol;
-        p.exi[11] = it.tn;
+        p.ex[ring_l0::kTCopy] = it.tcopy;
+        p.exi[ring_l0::kTCol] = it.tcol;
+        p.exi[ring_l0::kTN] = it.tn;
       }
-      if (gather && !l0) {
+      if (gather) {                               // ring outputs (kProGather / kProL0G)
         TD3_ARG(it.ring_src >= 0 && !lnin && ro, "internal: ring-sampled layer without a record field");
-        p.exi[0] = it.ring_src;
-        p.Aout = ro[k].a;
-        p.ldao = ro[k].lda;
-        p.ex[0] = ro[k].b;
-        p.exi[3] = ro[k].ldb;
-        p.ex[1] = ro[k].r;
-        p.ex[2] = ro[k].nd;
-        p.exi[1] = o_r;
+        p.exi[ring_l0::kRecOff] = it.ring_src;
+        if (l0) {                                 // the first copy of the row: kProGather stores it to Aout
+          p.ex[ring_l0::kRowCopy] = ro[k].a;
+          p.exi[ring_l0::kLdRowCopy] = ro[k].lda;
+        } else {
+          p.Aout = ro[k].a;
+          p.ldao = ro[k].lda;
+        }
+        p.ex[ring_l0::kRowCopy2] = ro[k].b;
+        p.exi[ring_l0::kLdRowCopy2] = ro[k].ldb;
+        p.ex[ring_l0::kReward] = ro[k].r;
+        p.ex[ring_l0::kNotDone] = ro[k].nd;
+        p.exi[ring_l0::kRecOffRw] = o_r;
       }
-      if (l0) {                                   // layer-0 operands (kernels.h kProL0 slots)
+      if (l0) {                                   // layer-0 operands
         const LinearL& L0 = it.net->lin[0];
         if (!gather) {
           p.A = it.e->X;
           p.lda = it.e->ldx;
         }
-        p.ex[8] = const_cast<float*>(it.P + L0.offW);
-        p.ex[9] = const_cast<float*>(it.P + L0.offb);
-        p.ex[10] = (it.stats || (!norm && it.store_u)) ? it.e->H[0] : nullptr;
-        p.exi[5] = L0.Np;
-        p.exi[6] = L0.K;
-        if (gather) {
-          TD3_ARG(it.ring_src >= 0 && ro, "internal: ring-sampled layer without a record field");
-          p.exi[0] = it.ring_src;
-          p.ex[3] = ro[k].a;
-          p.exi[8] = ro[k].lda;
-          p.ex[0] = ro[k].b;
-          p.exi[3] = ro[k].ldb;
-          p.ex[1] = ro[k].r;
-          p.ex[2] = ro[k].nd;
-          p.exi[1] = o_r;
-        }
+        p.ex[ring_l0::kW0] = const_cast<float*>(it.P + L0.offW);
+        p.ex[ring_l0::kB0] = const_cast<float*>(it.P + L0.offb);
+        p.ex[ring_l0::kH0] = (it.stats || (!norm && it.store_u)) ? it.e->H[0] : nullptr;
+        p.exi[ring_l0::kN0p] = L0.Np;
+        p.exi[ring_l0::kK0] = L0.K;
       }
       p.Kreal = L.K;
       p.Kp = L.Kp;
@@ -884,7 +882,7 @@ static int add_fwd_stages(td3_handle* h, std::vector<void*>& owned, std::vector<
         p.ldw = 4;
         p.wsk = 4 * L.Np;
         if (l0) {
-          p.ex[8] = const_cast<float*>(q + it.net->lin[0].offW);
+          p.ex[ring_l0::kW0] = const_cast<float*>(q + it.net->lin[0].offW);
           p.w0sk = 4 * it.net->lin[0].Np;
         }
       }
@@ -943,7 +941,7 @@ static int add_fwd_stages(td3_handle* h, std::vector<void*>& owned, std::vector<
         st.push_back({name, [=](hipStream_t s) { return launch_l0r16(nct, wk, 0, t, nb16, Bp, bmp, bump_actor, s); },
                       flops, kname});
       }
-      st.back().bytes = gemm_bytes(t.p, t.nprob);
+      st.back().bytes = gemm_bytes(t.p, t.nprob, pro);
       continue;
     }
     TD3_RC(push_gemm_stage(h, owned, st, probs, 0, wn, pro, Bp, lds, blocks, flops,
@@ -990,10 +988,10 @@ static int add_bwd_stages(td3_handle* h, std::vector<void*>& owned, std::vector<
         p.lda = L.Np;
         p.lng = it.P + n.ln[2].offg;
         p.lnb = it.P + n.ln[2].offb;
-        p.ex[3] = const_cast<float*>(it.P + n.lin[3].offW);
-        p.ex[4] = const_cast<float*>(it.P + n.lin[3].offb);
-        p.ex[5] = it.e->Qv;
-        p.exf[0] = head_bwd_scale;
+        p.ex[head_bwd_pro::kW4] = const_cast<float*>(it.P + n.lin[3].offW);
+        p.ex[head_bwd_pro::kB4] = const_cast<float*>(it.P + n.lin[3].offb);
+        p.ex[head_bwd_pro::kQ] = it.e->Qv;
+        p.exf[head_bwd_pro::kGradScale] = head_bwd_scale;
       } else if (l == 2) {                // dZ2 rows come from the loss / head row kernel
         p.A = it.e->GZ[2];
         p.lda = L.Np;
@@ -1033,13 +1031,13 @@ static int add_bwd_stages(td3_handle* h, std::vector<void*>& owned, std::vector<
       GemmProb p{};
       p.norm = norm ? 1 : 0;
       p.B = B;
-      p.ex[0] = it.e->GU[0];
-      p.ex[1] = it.e->H[0];
-      p.ex[2] = it.e->stats[0];
-      p.ex[3] = const_cast<float*>(it.P + it.net->ln[0].offg);
-      p.ex[4] = it.e->GZ[0];
-      p.exi[0] = L.Np;
-      p.exi[1] = L.N;
+      p.ex[ln_bwd::kDU] = it.e->GU[0];
+      p.ex[ln_bwd::kH] = it.e->H[0];
+      p.ex[ln_bwd::kStats] = it.e->stats[0];
+      p.ex[ln_bwd::kGamma] = const_cast<float*>(it.P + it.net->ln[0].offg);
+      p.ex[ln_bwd::kDZ] = it.e->GZ[0];
+      p.exi[ln_bwd::kLd] = L.Np;
+      p.exi[ln_bwd::kK] = L.N;
       lnbwd_rows->push_back(p);
     }
     return 0;
@@ -1559,12 +1557,75 @@ static size_t eval_floats(const NetL& n, int Bp, bool bwd, bool norm) {
   return f;
 }
 
-// Critic phase on unit loss gradients (kRowUnitLoss / kRowTargetLoss, row-scaled dW): off keeps
-// the sequential order (heads -> target twin -> critic_loss -> input grads -> dW).
-#ifndef TD3_UNIT_CRITIC
-#define TD3_UNIT_CRITIC 1
-#endif
-constexpr bool kUnitCritic = TD3_UNIT_CRITIC != 0;
+// The LN3 + head operands (ln3_head slots) of network n (arena Pp) evaluated into e
+static void set_ln3_head(GemmProb& p, const float* Pp, const NetL& n, const EvalB& e) {
+  p.ex[ln3_head::kH3] = e.H[2];
+  p.ex[ln3_head::kGamma3] = const_cast<float*>(Pp + n.ln[2].offg);
+  p.ex[ln3_head::kBeta3] = const_cast<float*>(Pp + n.ln[2].offb);
+  p.ex[ln3_head::kW4] = const_cast<float*>(Pp + n.lin[3].offW);
+  p.ex[ln3_head::kB4] = const_cast<float*>(Pp + n.lin[3].offb);
+  p.exi[ln3_head::kK3] = n.lin[2].N;
+  p.exi[ln3_head::kLd3] = n.lin[2].Np;
+}
+
+// The actor's head / LN3 operands and outputs shared by kRowActorHeadBwd and kRowActorHeadBwdP
+// (actor_bwd slots): the actor (arena Pa) evaluated into e, its action at column acol of the Q1 input
+static void set_actor_bwd(GemmProb& p, const float* Pa, const NetL& an, const EvalB& e, int acol, int ad,
+                          float max_action) {
+  p.ex[actor_bwd::kTanh] = e.T;
+  p.ex[actor_bwd::kW4] = const_cast<float*>(Pa + an.lin[3].offW);
+  p.ex[actor_bwd::kH3] = e.H[2];
+  p.ex[actor_bwd::kStats3] = e.stats[2];
+  p.ex[actor_bwd::kGamma3] = const_cast<float*>(Pa + an.ln[2].offg);
+  p.ex[actor_bwd::kDZ4] = e.GZ[3];
+  p.ex[actor_bwd::kDU3] = e.GU[2];
+  p.Aout = e.GZ[2];
+  p.ldao = an.lin[2].Np;
+  p.exi[actor_bwd::kActCol] = acol;
+  p.exi[actor_bwd::kAd] = ad;
+  p.exi[actor_bwd::kK3] = an.lin[2].N;
+  p.exi[actor_bwd::kLd3] = an.lin[2].Np;
+  p.exi[actor_bwd::kLdw4] = an.lin[3].Kp;
+  p.exf[actor_bwd::kMaxAction] = max_action;
+}
+
+// Where a policy head puts its action, and how: columns [acol, acol + ad) of the ld-strided rows of
+// out (and out2, nullable); clamp: a' to +-max_action
+struct PolicyDst {
+  float* out; float* out2; int ld, acol;
+  int clamp; float max_action;
+};
+// kRowPolicyHead problem: the actor (arena Pp) evaluated into e; target: smoothing noise (drawn
+// here when gen_noise, else read from the plan's noise rows)
+static GemmProb policy_head_prob(const td3_handle* h, const Plan& pl, const float* Pp, const EvalB& e,
+                                 const PolicyDst& d, int target, int gen_noise) {
+  namespace ph = policy_head;
+  const NetL& an = h->actor.nets[0];
+  GemmProb p{};
+  p.norm = h->cfg.norm == 1 ? 1 : 0;
+  p.B = pl.B;
+  set_ln3_head(p, Pp, an, e);
+  p.ex[ph::kNoise] = pl.noise;
+  p.ex[ph::kOut] = d.out;
+  p.ex[ph::kTanh] = e.T;
+  p.ex[ph::kU3] = e.U[2];
+  p.ex[ph::kStats3] = e.stats[2];
+  p.ex[ph::kOut2] = d.out2;
+  p.exi[ph::kLdw4] = an.lin[3].Kp;
+  p.exi[ph::kLdOut] = d.ld;
+  p.exi[ph::kGenNoise] = gen_noise;
+  p.exi[ph::kAd] = h->ad;
+  p.exi[ph::kActCol] = d.acol;
+  p.exi[ph::kLdNoise] = h->ad;
+  p.exi[ph::kTarget] = target;
+  p.exi[ph::kClamp] = d.clamp;
+  p.exf[ph::kMaxAction] = d.max_action;
+  p.exf[ph::kPolicyNoise] = (float)h->cfg.policy_noise;
+  p.exf[ph::kNoiseClip] = (float)h->cfg.noise_clip;
+  p.seed = h->cfg.seed;
+  p.ctr = h->d_ctr;
+  return p;
+}
 
 static int build_step(td3_handle* h, int B) {
   std::unique_ptr<Plan> P(new Plan());
@@ -1627,37 +1688,9 @@ static int build_step(td3_handle* h, int B) {
   const float* Ptq2 = h->critic.T;
 
   const float ma = h->cfg.max_action;
-  // policy-head row operands (row_policy_head in kernels.hip)
+  // a' = clamp(ma tanh + noise) (TD3_featured.py:131-137) / pi(s) into the action columns of a critic input
   auto policy_head = [&](const float* Pp, EvalB& e, float* out, int target, int gen_noise) {
-    GemmProb p{};
-    p.norm = norm ? 1 : 0;
-    p.B = B;
-    p.ex[0] = e.H[2];
-    p.ex[1] = const_cast<float*>(Pp + an.ln[2].offg);
-    p.ex[2] = const_cast<float*>(Pp + an.ln[2].offb);
-    p.ex[3] = const_cast<float*>(Pp + an.lin[3].offW);
-    p.ex[4] = const_cast<float*>(Pp + an.lin[3].offb);
-    p.ex[5] = P->noise;
-    p.ex[6] = out;
-    p.ex[7] = e.T;
-    p.ex[8] = e.U[2];
-    p.ex[9] = e.stats[2];
-    p.exi[0] = an.lin[2].N;
-    p.exi[1] = an.lin[2].Np;
-    p.exi[2] = an.lin[3].Kp;
-    p.exi[3] = P->ld_sa;
-    p.exi[4] = gen_noise;
-    p.exi[5] = ad;
-    p.exi[6] = sd;
-    p.exi[7] = ad;
-    p.exi[8] = target;
-    p.exi[9] = 1;                                  // clamp a' to +-max_action (TD3_featured.py:135-137)
-    p.exf[0] = ma;
-    p.exf[1] = (float)h->cfg.policy_noise;
-    p.exf[2] = (float)h->cfg.noise_clip;
-    p.seed = h->cfg.seed;
-    p.ctr = h->d_ctr;
-    return p;
+    return policy_head_prob(h, *P, Pp, e, {out, nullptr, P->ld_sa, sd, 1, ma}, target, gen_noise);
   };
 
   for (int actor_phase = 0; actor_phase < 2; ++actor_phase) {
@@ -1687,143 +1720,77 @@ static int build_step(td3_handle* h, int B) {
                               2 * sd + ad, true, true));
         P->body_ring[actor_phase][inj].push_back(fr[0]);
       }
-      if (kUnitCritic) {
-        // Critic phase on unit loss gradients (kRowUnitLoss): the twin's input-grad chain runs
-        // between the heads and the target twin, independent of y; the target-loss row stage
-        // (y, g_j = 2/B (Q_j - y)) shares its launch with the layer-0 LN backward rows, and the
-        // dW stage scales the unit rows by g_j.  One launch fewer than the sequential order.
-        {
-          std::vector<GemmProb> hp = {policy_head(Pta, P->TA, P->X_S2A, 1, inj ? 0 : 1)};
-          if (actor_phase) hp.push_back(policy_head(Pa, P->A, P->X_SP, 0, 0));
-          const int n1 = (int)hp.size();
-          for (int j = 0; j < 2; ++j) {
-            const NetL& qj = j ? q2 : q1;
-            GemmProb p{};
-            p.norm = norm ? 1 : 0;
-            p.B = B;
-            p.ex[0] = P->Q[j].H[2];
-            p.ex[1] = const_cast<float*>(Pq1 + qj.ln[2].offg);
-            p.ex[2] = const_cast<float*>(Pq1 + qj.ln[2].offb);
-            p.ex[3] = const_cast<float*>(Pq1 + qj.lin[3].offW);
-            p.ex[4] = const_cast<float*>(Pq1 + qj.lin[3].offb);
-            p.ex[5] = P->Q[j].Qv;
-            p.ex[6] = P->Q[j].U[2];
-            p.ex[7] = P->Q[j].stats[2];
-            p.ex[8] = P->Q[j].GU[2];
-            p.Aout = P->Q[j].GZ[2];
-            p.ldao = qj.lin[2].Np;
-            p.exi[0] = qj.lin[2].N;
-            p.exi[1] = qj.lin[2].Np;
-            hp.push_back(p);
-          }
-          TD3_RC(push_row2_stage(st, hp, kRowPolicyHead, kRowUnitLoss, n1, Bp, "heads"));
-        }
-        std::vector<BwdItem> cb = {{&q1, Pq1, &P->Q[0], true}, {&q2, Pq2, &P->Q[1], true}};
-        std::vector<GemmProb> rows;
-        {   // the target loss row problem first (kRowTargetLoss), the LN0 backward rows after it
+      // Critic phase on unit loss gradients (kRowUnitLoss): the twin's input-grad chain runs
+      // between the heads and the target twin, independent of y; the target-loss row stage
+      // (y, g_j = 2/B (Q_j - y)) shares its launch with the layer-0 LN backward rows, and the
+      // dW stage scales the unit rows by g_j.  One launch fewer than the sequential order
+      // (heads -> target twin -> critic loss -> input grads -> dW).
+      {
+        std::vector<GemmProb> hp = {policy_head(Pta, P->TA, P->X_S2A, 1, inj ? 0 : 1)};
+        if (actor_phase) hp.push_back(policy_head(Pa, P->A, P->X_SP, 0, 0));
+        const int n1 = (int)hp.size();
+        for (int j = 0; j < 2; ++j) {
+          const NetL& qj = j ? q2 : q1;
           GemmProb p{};
           p.norm = norm ? 1 : 0;
           p.B = B;
-          p.ex[0] = P->TQ[0].H[2];
-          p.ex[1] = P->TQ[1].H[2];
-          p.ex[2] = const_cast<float*>(Ptq1 + q1.ln[2].offg);
-          p.ex[3] = const_cast<float*>(Ptq2 + q2.ln[2].offg);
-          p.ex[4] = const_cast<float*>(Ptq1 + q1.ln[2].offb);
-          p.ex[5] = const_cast<float*>(Ptq2 + q2.ln[2].offb);
-          p.ex[6] = const_cast<float*>(Ptq1 + q1.lin[3].offW);
-          p.ex[7] = const_cast<float*>(Ptq2 + q2.lin[3].offW);
-          p.ex[8] = const_cast<float*>(Ptq1 + q1.lin[3].offb);
-          p.ex[9] = const_cast<float*>(Ptq2 + q2.lin[3].offb);
-          p.ex[10] = P->R;
-          p.ex[11] = P->ND;
-          p.ex[12] = P->Q[0].Qv;
-          p.ex[13] = P->Q[1].Qv;
-          p.ex[14] = P->Y;
-          p.ex[15] = P->Q[0].GZ[3];
-          p.ex[16] = P->Q[1].GZ[3];
-          p.ex[17] = P->sqerr;
-          p.ex[18] = P->gscale[0];
-          p.ex[19] = P->gscale[1];
-          p.exi[0] = q1.lin[2].N;
-          p.exi[1] = q1.lin[2].Np;
-          p.exf[0] = (float)h->cfg.discount;
-          p.exf[1] = (float)(2.0 / (double)B);
-          rows.push_back(p);
+          set_ln3_head(p, Pq1, qj, P->Q[j]);
+          p.ex[unit_loss::kQ] = P->Q[j].Qv;
+          p.ex[unit_loss::kU3] = P->Q[j].U[2];
+          p.ex[unit_loss::kStats3] = P->Q[j].stats[2];
+          p.ex[unit_loss::kDU3] = P->Q[j].GU[2];
+          p.Aout = P->Q[j].GZ[2];
+          p.ldao = qj.lin[2].Np;
+          hp.push_back(p);
         }
-        TD3_RC(add_bwd_stages(h, P->tables, st, cb, Bp, B, "CB", true, false, &rows));
-        std::vector<FwdItem> f2 = {{&q1, Ptq1, &P->TQ[0], false, false}, {&q2, Ptq2, &P->TQ[1], false, false}};
-        TD3_RC(add_fwd_stages(h, P->tables, st, f2, Bp, B, "TF", nullptr, 0, nullptr, nullptr, 0, true));
-        {   // the unit backward's input-grad stages share launches with the target twin's layers, in
-            // order: TF layer k moves up to CB stage k only while every earlier TF layer moved too
-          const char* cbn[2] = {"CB_bwd2", "CB_bwd1"};
-          std::vector<std::string> tfn;
-          for (const char* n : {"TF_fwd0", "TF_fwd01", "TF_fwd1", "TF_fwd2"})
-            if (stage_index(st, n) >= 0) tfn.push_back(n);
-          for (size_t k = 0; k < 2 && k < tfn.size(); ++k) {
-            const int i = stage_index(st, cbn[k]), j = stage_index(st, tfn[k]);
-            if (i < 0 || j <= i || !merge_gemm_pair(st, (size_t)i, (size_t)j)) break;
-          }
-        }
-        TD3_RC(push_row2_stage(st, rows, kRowTargetLoss, kRowLnBwd, 1, Bp, "critic_loss"));
-        const std::vector<const float*> usc = {P->gscale[0], P->gscale[1]};
-        TD3_RC(add_dw_stage(h, P->tables, st, h->critic, 0, cb, Bp, "C", actor_phase != 0, 0, &usc, &P->dwslab));
-      } else {
-        // ---- heads: a' = target smoothing into X_S2A (:131-137); pi(s) into X_SP (:159)
-        {
-          std::vector<GemmProb> hp = {policy_head(Pta, P->TA, P->X_S2A, 1, inj ? 0 : 1)};
-          if (actor_phase) hp.push_back(policy_head(Pa, P->A, P->X_SP, 0, 0));
-          TD3_RC(push_row_stage(h, P->tables, st, hp, kRowPolicyHead, Bp, "heads"));
-        }
-        // ---- target twin on (s', a')
-        std::vector<FwdItem> f2 = {{&q1, Ptq1, &P->TQ[0], false, false}, {&q2, Ptq2, &P->TQ[1], false, false}};
-        TD3_RC(add_fwd_stages(h, P->tables, st, f2, Bp, B, "TF", nullptr, 0, nullptr, nullptr, 0, true));
-        // ---- critic loss (clipped double-Q target, mse) and LN3 backward of the twin
-        {
-          std::vector<GemmProb> cl;
-          for (int j = 0; j < 2; ++j) {
-            const NetL& qj = j ? q2 : q1;
-            GemmProb p{};
-            p.norm = norm ? 1 : 0;
-            p.B = B;
-            p.ex[0] = P->TQ[0].H[2];
-            p.ex[1] = P->TQ[1].H[2];
-            p.ex[2] = P->Q[j].H[2];
-            p.ex[3] = const_cast<float*>(Ptq1 + q1.ln[2].offg);
-            p.ex[4] = const_cast<float*>(Ptq2 + q2.ln[2].offg);
-            p.ex[5] = const_cast<float*>(Pq1 + qj.ln[2].offg);
-            p.ex[6] = const_cast<float*>(Ptq1 + q1.ln[2].offb);
-            p.ex[7] = const_cast<float*>(Ptq2 + q2.ln[2].offb);
-            p.ex[8] = const_cast<float*>(Pq1 + qj.ln[2].offb);
-            p.ex[9] = const_cast<float*>(Ptq1 + q1.lin[3].offW);
-            p.ex[10] = const_cast<float*>(Ptq2 + q2.lin[3].offW);
-            p.ex[11] = const_cast<float*>(Pq1 + qj.lin[3].offW);
-            p.ex[12] = const_cast<float*>(Ptq1 + q1.lin[3].offb);
-            p.ex[13] = const_cast<float*>(Ptq2 + q2.lin[3].offb);
-            p.ex[14] = const_cast<float*>(Pq1 + qj.lin[3].offb);
-            p.ex[15] = P->R;
-            p.ex[16] = P->ND;
-            p.ex[17] = P->Q[j].GZ[3];
-            p.ex[18] = P->Q[j].GU[2];
-            p.ex[19] = P->Q[j].U[2];
-            p.ex[20] = P->Q[j].stats[2];
-            p.ex[21] = P->Y;
-            p.ex[22] = P->sqerr + (size_t)j * Bp;
-            p.ex[23] = P->Q[j].Qv;
-            p.Aout = P->Q[j].GZ[2];
-            p.ldao = qj.lin[2].Np;
-            p.exi[0] = qj.lin[2].N;
-            p.exi[1] = qj.lin[2].Np;
-            p.exi[2] = j;
-            p.exf[0] = (float)h->cfg.discount;
-            p.exf[1] = (float)(2.0 / (double)B);
-            cl.push_back(p);
-          }
-          TD3_RC(push_row_stage(h, P->tables, st, cl, kRowCriticLoss, Bp, "critic_loss"));
-        }
-        std::vector<BwdItem> cb = {{&q1, Pq1, &P->Q[0], true}, {&q2, Pq2, &P->Q[1], true}};
-        TD3_RC(add_bwd_stages(h, P->tables, st, cb, Bp, B, "CB", true));
-        TD3_RC(add_dw_stage(h, P->tables, st, h->critic, 0, cb, Bp, "C", actor_phase != 0, 0, nullptr, &P->dwslab));
+        TD3_RC(push_row2_stage(st, hp, kRowPolicyHead, kRowUnitLoss, n1, Bp, "heads"));
       }
+      std::vector<BwdItem> cb = {{&q1, Pq1, &P->Q[0], true}, {&q2, Pq2, &P->Q[1], true}};
+      std::vector<GemmProb> rows;
+      {   // the target loss row problem first (kRowTargetLoss), the LN0 backward rows after it
+        GemmProb p{};
+        p.norm = norm ? 1 : 0;
+        p.B = B;
+        namespace tl = target_loss;
+        for (int j = 0; j < 2; ++j) {
+          const NetL& qj = j ? q2 : q1;
+          const float* Ptq = j ? Ptq2 : Ptq1;
+          p.ex[tl::kH3 + j] = P->TQ[j].H[2];
+          p.ex[tl::kGamma3 + j] = const_cast<float*>(Ptq + qj.ln[2].offg);
+          p.ex[tl::kBeta3 + j] = const_cast<float*>(Ptq + qj.ln[2].offb);
+          p.ex[tl::kW4 + j] = const_cast<float*>(Ptq + qj.lin[3].offW);
+          p.ex[tl::kB4 + j] = const_cast<float*>(Ptq + qj.lin[3].offb);
+          p.ex[tl::kQ + j] = P->Q[j].Qv;
+          p.ex[tl::kDZ4 + j] = P->Q[j].GZ[3];
+          p.ex[tl::kG + j] = P->gscale[j];
+        }
+        p.ex[tl::kReward] = P->R;
+        p.ex[tl::kNotDone] = P->ND;
+        p.ex[tl::kY] = P->Y;
+        p.ex[tl::kSqErr] = P->sqerr;
+        p.exi[tl::kK3] = q1.lin[2].N;
+        p.exi[tl::kLd3] = q1.lin[2].Np;
+        p.exf[tl::kDiscount] = (float)h->cfg.discount;
+        p.exf[tl::kGradScale] = (float)(2.0 / (double)B);
+        rows.push_back(p);
+      }
+      TD3_RC(add_bwd_stages(h, P->tables, st, cb, Bp, B, "CB", true, false, &rows));
+      std::vector<FwdItem> f2 = {{&q1, Ptq1, &P->TQ[0], false, false}, {&q2, Ptq2, &P->TQ[1], false, false}};
+      TD3_RC(add_fwd_stages(h, P->tables, st, f2, Bp, B, "TF", nullptr, 0, nullptr, nullptr, 0, true));
+      {   // the unit backward's input-grad stages share launches with the target twin's layers, in
+          // order: TF layer k moves up to CB stage k only while every earlier TF layer moved too
+        const char* cbn[2] = {"CB_bwd2", "CB_bwd1"};
+        std::vector<std::string> tfn;
+        for (const char* n : {"TF_fwd0", "TF_fwd01", "TF_fwd1", "TF_fwd2"})
+          if (stage_index(st, n) >= 0) tfn.push_back(n);
+        for (size_t k = 0; k < 2 && k < tfn.size(); ++k) {
+          const int i = stage_index(st, cbn[k]), j = stage_index(st, tfn[k]);
+          if (i < 0 || j <= i || !merge_gemm_pair(st, (size_t)i, (size_t)j)) break;
+        }
+      }
+      TD3_RC(push_row2_stage(st, rows, kRowTargetLoss, kRowLnBwd, 1, Bp, "critic_loss"));
+      const std::vector<const float*> usc = {P->gscale[0], P->gscale[1]};
+      TD3_RC(add_dw_stage(h, P->tables, st, h->critic, 0, cb, Bp, "C", actor_phase != 0, 0, &usc, &P->dwslab));
       if (!actor_phase) continue;
       // ---------------- delayed policy update (TD3_featured.py:156-171)
       std::vector<FwdItem> f3 = {{&q1, Pq1, &P->AQ, false, true}};
@@ -1835,38 +1802,25 @@ static int build_step(td3_handle* h, int B) {
       }
       TD3_RC(add_fwd_stages(h, P->tables, st, f3, Bp, B, "AF", nullptr, 0, nullptr, nullptr, 0, true, true));
       // the actor loss -mean Q1(s, pi(s)) (:159): Q1's head and its backward are the prologue of
-      // AQB_bwd2 (kProHeadBwd; the row launch kRowActorLoss is the particle path's)
+      // AQB_bwd2 (kProHeadBwd; the particle path has the row launch kRowActorLossP instead)
       std::vector<BwdItem> aqb = {{&q1, Pq1, &P->AQ, false}};
       TD3_RC(add_bwd_stages(h, P->tables, st, aqb, Bp, B, "AQB", false, false, nullptr, (float)(-1.0) / (float)B));
       {
         GemmProb p{};
         p.norm = norm ? 1 : 0;
         p.B = B;
-        p.ex[0] = P->AQ.GU[0];
-        p.ex[1] = P->AQ.H[0];
-        p.ex[2] = P->AQ.stats[0];
-        p.ex[3] = const_cast<float*>(Pq1 + q1.ln[0].offg);
-        p.ex[4] = const_cast<float*>(Pq1 + q1.lin[0].offW);
-        p.ex[5] = P->A.T;
-        p.ex[6] = const_cast<float*>(Pa + an.lin[3].offW);
-        p.ex[7] = P->A.H[2];
-        p.ex[8] = P->A.stats[2];
-        p.ex[9] = const_cast<float*>(Pa + an.ln[2].offg);
-        p.ex[10] = P->A.GZ[3];
-        p.ex[11] = P->A.GU[2];
-        p.ex[12] = w1at ? P->W1aT : nullptr;      // the action columns as rows (AF_fwd0 wrote them)
-        p.Aout = P->A.GZ[2];
-        p.ldao = an.lin[2].Np;
-        p.exi[8] = q1.lin[0].Np;
-        p.exi[0] = q1.lin[0].N;
-        p.exi[1] = q1.lin[0].Np;
-        p.exi[2] = q1.lin[0].Kp;
-        p.exi[3] = sd;
-        p.exi[4] = ad;
-        p.exi[5] = an.lin[2].N;
-        p.exi[6] = an.lin[2].Np;
-        p.exi[7] = an.lin[3].Kp;
-        p.exf[0] = ma;
+        namespace ab = actor_head_bwd;
+        p.ex[ab::kDU0] = P->AQ.GU[0];
+        p.ex[ab::kH0] = P->AQ.H[0];
+        p.ex[ab::kStats0] = P->AQ.stats[0];
+        p.ex[ab::kGamma0] = const_cast<float*>(Pq1 + q1.ln[0].offg);
+        p.ex[ab::kW1] = const_cast<float*>(Pq1 + q1.lin[0].offW);
+        p.ex[ab::kW1T] = w1at ? P->W1aT : nullptr;      // the action columns as rows (AF_fwd0 wrote them)
+        p.exi[ab::kLdW1T] = q1.lin[0].Np;
+        p.exi[ab::kK0] = q1.lin[0].N;
+        p.exi[ab::kLd0] = q1.lin[0].Np;
+        p.exi[ab::kLdw1] = q1.lin[0].Kp;
+        set_actor_bwd(p, Pa, an, P->A, sd, ad, ma);
         std::vector<GemmProb> v = {p};
         TD3_RC(push_row_stage(h, P->tables, st, v, kRowActorHeadBwd, Bp, "actor_head_bwd"));
       }
@@ -2071,37 +2025,9 @@ static int build_step_particles(td3_handle* h, int B) {
   const float* Ptq = h->critic.T;
   const int acol = kEncC2 + F;        // first action column of the Q input rows (TD3_particles.py:110)
 
+  // no clamp of a' (TD3_particles.py:179-181), tanh output (:68)
   auto policy_head = [&](const float* Pp, EvalB& e, float* out, float* out2, int target, int gen_noise) {
-    GemmProb p{};
-    p.norm = norm ? 1 : 0;
-    p.B = B;
-    p.ex[0] = e.H[2];
-    p.ex[1] = const_cast<float*>(Pp + an.ln[2].offg);
-    p.ex[2] = const_cast<float*>(Pp + an.ln[2].offb);
-    p.ex[3] = const_cast<float*>(Pp + an.lin[3].offW);
-    p.ex[4] = const_cast<float*>(Pp + an.lin[3].offb);
-    p.ex[5] = P->noise;
-    p.ex[6] = out;
-    p.ex[7] = e.T;
-    p.ex[8] = e.U[2];
-    p.ex[9] = e.stats[2];
-    p.ex[10] = out2;
-    p.exi[0] = an.lin[2].N;
-    p.exi[1] = an.lin[2].Np;
-    p.exi[2] = an.lin[3].Kp;
-    p.exi[3] = P->ld_q;
-    p.exi[4] = gen_noise;
-    p.exi[5] = ad;
-    p.exi[6] = acol;
-    p.exi[7] = ad;
-    p.exi[8] = target;
-    p.exi[9] = 0;                                  // no clamp of a' (TD3_particles.py:179-181)
-    p.exf[0] = 1.0f;                               // tanh output (:68)
-    p.exf[1] = (float)h->cfg.policy_noise;
-    p.exf[2] = (float)h->cfg.noise_clip;
-    p.seed = h->cfg.seed;
-    p.ctr = h->d_ctr;
-    return p;
+    return policy_head_prob(h, *P, Pp, e, {out, out2, P->ld_q, acol, 0, 1.0f}, target, gen_noise);
   };
 
   // ---------------- delayed policy update (TD3_particles.py:206-224): _actor_learn on (s features, s
@@ -2115,19 +2041,13 @@ static int build_step_particles(td3_handle* h, int B) {
       GemmProb p{};
       p.norm = norm ? 1 : 0;
       p.B = B;
-      p.ex[0] = P->AQ.H[2];
-      p.ex[1] = const_cast<float*>(Pq + q1.ln[2].offg);
-      p.ex[2] = const_cast<float*>(Pq + q1.ln[2].offb);
-      p.ex[3] = const_cast<float*>(Pq + q1.lin[3].offW);
-      p.ex[4] = const_cast<float*>(Pq + q1.lin[3].offb);
-      p.ex[5] = P->AQ.Qv;
+      set_ln3_head(p, Pq, q1, P->AQ);
+      p.ex[actor_loss_p::kQ] = P->AQ.Qv;
       p.Aout = P->AQ.GZ[2];
       p.ldao = q1.lin[2].Np;
-      p.exi[0] = q1.lin[2].N;
-      p.exi[1] = q1.lin[2].Np;
-      p.exi[2] = ad;
-      p.exi[3] = q1.lin[3].Kp;
-      p.exf[0] = (float)(-1.0 / ((double)B * ad));
+      p.exi[actor_loss_p::kNq] = ad;
+      p.exi[actor_loss_p::kLdw4] = q1.lin[3].Kp;
+      p.exf[actor_loss_p::kGradScale] = (float)(-1.0 / ((double)B * ad));
       std::vector<GemmProb> v = {p};
       TD3_RC(push_row_stage(h, P->tables, st, v, kRowActorLossP, Bp, "actor_loss"));
     }
@@ -2137,27 +2057,14 @@ static int build_step_particles(td3_handle* h, int B) {
       GemmProb p{};
       p.norm = norm ? 1 : 0;
       p.B = B;
-      p.ex[0] = P->AQ.GUin;
-      p.ex[1] = P->XAQ;
-      p.ex[2] = P->AQ.statsIn;
-      p.ex[3] = const_cast<float*>(Pq + q1.ln_in.offg);
-      p.ex[5] = P->A.T;
-      p.ex[6] = const_cast<float*>(Pa + an.lin[3].offW);
-      p.ex[7] = P->A.H[2];
-      p.ex[8] = P->A.stats[2];
-      p.ex[9] = const_cast<float*>(Pa + an.ln[2].offg);
-      p.ex[10] = P->A.GZ[3];
-      p.ex[11] = P->A.GU[2];
-      p.Aout = P->A.GZ[2];
-      p.ldao = an.lin[2].Np;
-      p.exi[0] = q1.lin[0].K;
-      p.exi[1] = q1.lin[0].Kp;
-      p.exi[3] = acol;
-      p.exi[4] = ad;
-      p.exi[5] = an.lin[2].N;
-      p.exi[6] = an.lin[2].Np;
-      p.exi[7] = an.lin[3].Kp;
-      p.exf[0] = 1.0f;
+      namespace ab = actor_head_bwd_p;
+      p.ex[ab::kDUin] = P->AQ.GUin;
+      p.ex[ab::kXin] = P->XAQ;
+      p.ex[ab::kStatsIn] = P->AQ.statsIn;
+      p.ex[ab::kGammaIn] = const_cast<float*>(Pq + q1.ln_in.offg);
+      p.exi[ab::kKin] = q1.lin[0].K;
+      p.exi[ab::kLdIn] = q1.lin[0].Kp;
+      set_actor_bwd(p, Pa, an, P->A, acol, ad, 1.0f);
       std::vector<GemmProb> v = {p};
       TD3_RC(push_row_stage(h, P->tables, st, v, kRowActorHeadBwdP, Bp, "actor_head_bwd"));
     }
@@ -2205,40 +2112,37 @@ static int build_step_particles(td3_handle* h, int B) {
           GemmProb p{};
           p.norm = norm ? 1 : 0;
           p.B = B;
-          p.ex[0] = P->TQ[0].H[2];
-          p.ex[1] = T1.H[2];
-          p.ex[2] = P->Q[j].H[2];
-          p.ex[3] = const_cast<float*>(Ptq + q1.ln[2].offg);
-          p.ex[4] = const_cast<float*>(Ptq + t1.ln[2].offg);
-          p.ex[5] = const_cast<float*>(Pq + qj.ln[2].offg);
-          p.ex[6] = const_cast<float*>(Ptq + q1.ln[2].offb);
-          p.ex[7] = const_cast<float*>(Ptq + t1.ln[2].offb);
-          p.ex[8] = const_cast<float*>(Pq + qj.ln[2].offb);
-          p.ex[9] = const_cast<float*>(Ptq + q1.lin[3].offW);
-          p.ex[10] = const_cast<float*>(Ptq + t1.lin[3].offW);
-          p.ex[11] = const_cast<float*>(Pq + qj.lin[3].offW);
-          p.ex[12] = const_cast<float*>(Ptq + q1.lin[3].offb);
-          p.ex[13] = const_cast<float*>(Ptq + t1.lin[3].offb);
-          p.ex[14] = const_cast<float*>(Pq + qj.lin[3].offb);
-          p.ex[15] = P->R;
-          p.ex[16] = P->ND;
-          p.ex[17] = P->Q[j].GZ[3];
-          p.ex[18] = P->Q[j].GU[2];
-          p.ex[19] = P->Q[j].U[2];
-          p.ex[20] = P->Q[j].stats[2];
-          p.ex[21] = P->Y;
-          p.ex[22] = P->sqerr + (size_t)j * Bp;
-          p.ex[23] = P->Q[j].Qv;
+          namespace cp = critic_loss_p;
+          // the three heads: target q1, target q2 (= target q1 without CDQ), online q_j
+          const NetL* hn[3] = {&q1, &t1, &qj};
+          const float* hp[3] = {Ptq, Ptq, Pq};
+          const EvalB* he[3] = {&P->TQ[0], &T1, &P->Q[j]};
+          for (int n = 0; n < 3; ++n) {
+            p.ex[cp::kH3 + n] = he[n]->H[2];
+            p.ex[cp::kGamma3 + n] = const_cast<float*>(hp[n] + hn[n]->ln[2].offg);
+            p.ex[cp::kBeta3 + n] = const_cast<float*>(hp[n] + hn[n]->ln[2].offb);
+            p.ex[cp::kW4 + n] = const_cast<float*>(hp[n] + hn[n]->lin[3].offW);
+            p.ex[cp::kB4 + n] = const_cast<float*>(hp[n] + hn[n]->lin[3].offb);
+          }
+          p.ex[cp::kReward] = P->R;
+          p.ex[cp::kNotDone] = P->ND;
+          p.ex[cp::kDZ4] = P->Q[j].GZ[3];
+          p.ex[cp::kDU3] = P->Q[j].GU[2];
+          p.ex[cp::kU3] = P->Q[j].U[2];
+          p.ex[cp::kStats3] = P->Q[j].stats[2];
+          p.ex[cp::kY] = P->Y;
+          p.ex[cp::kSqErr] = P->sqerr + (size_t)j * Bp;
+          p.ex[cp::kQ] = P->Q[j].Qv;
           p.Aout = P->Q[j].GZ[2];
           p.ldao = qj.lin[2].Np;
-          p.exi[0] = qj.lin[2].N;
-          p.exi[1] = qj.lin[2].Np;
-          p.exi[2] = j;
-          p.exi[3] = ad;
-          p.exi[4] = qj.lin[3].Kp;
-          p.exi[5] = cdq ? 1 : 0;
-          p.exf[0] = (float)h->cfg.discount;
-          p.exf[1] = (float)(2.0 / ((double)B * ad));
+          p.exi[cp::kK3] = qj.lin[2].N;
+          p.exi[cp::kLd3] = qj.lin[2].Np;
+          p.exi[cp::kJ] = j;
+          p.exi[cp::kNq] = ad;
+          p.exi[cp::kLdw4] = qj.lin[3].Kp;
+          p.exi[cp::kCdq] = cdq ? 1 : 0;
+          p.exf[cp::kDiscount] = (float)h->cfg.discount;
+          p.exf[cp::kGradScale] = (float)(2.0 / ((double)B * ad));
           cl.push_back(p);
         }
         TD3_RC(push_row_stage(h, P->tables, st, cl, kRowCriticLossP, Bp, "critic_loss"));
