@@ -82,6 +82,19 @@ def params_close(P, golden, prefix, salt_base, atol, rtol=1e-5, frac_loose=1e-3,
         assert err.max() <= loose, (prefix, k, err.max())
 
 
+def stage_kernels(pol, rb, B, actor_phase):
+    """[(stage name, HIP kernel)] of the learner's plan for batch B and that phase, stage 0 the
+    sample (td3_profile_stages: the production body, run once as a real step; GPU only)."""
+    import ctypes as C
+    from td3_amd import _lib
+    ms = (C.c_float * 128)()
+    n = C.c_int()
+    _lib.check(pol._lib.td3_profile_stages(pol._h, rb.handle, B, actor_phase, ms, 128, C.byref(n)),
+               "td3_profile_stages")
+    return [(pol._lib.td3_stage_name(pol._h, i).decode(), pol._lib.td3_stage_kernel(pol._h, i).decode())
+            for i in range(n.value)]
+
+
 def oracle_dp_step(L, batch, noise, n, step_fn=None):
     """The oracle's restatement of the product's data-parallel step: n Learner copies
     in lock-step (threads), replica k on rows [k*b, (k+1)*b) of the batch; each phase's gradients

@@ -1,8 +1,9 @@
 """Edge cases of the HIP step against the oracle (teacher-forced, SURVEY.md §8c tolerances).
 
 * ragged batches: B = 1, 33, 257 (row tiles of 32 with 31 / 31 / 31 padding rows), and the
-  64x64 dW tiles of B >= 512: B = 544 (Bp % 64 = 32: register-staged dw64_kernel) and B = 640
-  (LDS-DMA dw64g_kernel, whose 64-row steps need Bp % 64 = 0; edge tiles with dead quadrants);
+  64x64 dW tiles of B >= 512: B = 544 (Bp % 64 = 32: one tile per workgroup, the register-staged
+  dw64_kernel) and B = 640 (Bp % 64 = 0: the split-K persistent dwsk_kernel + its combine, td3.hip
+  TD3_DWSK / add_dw_stage; edge tiles with dead quadrants) -- the C_dw stage's kernel is asserted;
 * hidden widths other than the reference's (500, 400, 300) / (500, 400, 200): narrow, odd and
   the 512-wide maximum (every Linear / LayerNorm is padded to 32 in HBM, td3.hip);
 * the widest action space the heads take (32) and the widest network input (512 columns, a
@@ -16,26 +17,30 @@ tests/test_oracle_golden.py on the golden configs) is the checker.
 import numpy as np
 import pytest
 
-from helpers import gen, orc
+from helpers import gen, orc, stage_kernels
 from test_gpu_parity import Box, _params_close, _load_oracle_state, _rel_to_max
 
 pytestmark = pytest.mark.gpu
 
 
-def _setup(sd, ad, ma=1.0, norm="layer", actor_arch=gen.ACTOR_ARCH, q_arch=gen.Q_ARCH, rows=gen.BUFFER_ROWS):
+def _setup(sd, ad, ma=1.0, norm="layer", actor_arch=gen.ACTOR_ARCH, q_arch=gen.Q_ARCH, rows=gen.BUFFER_ROWS,
+           fill=None, rb_seed=0, use_graph="auto"):
+    """Learner, ring, oracle learner and host buffer of one configuration; ``fill`` rows (default:
+    all of them) of a ring of ``rows`` are written, ``rb_seed`` seeds the ring's Philox draw."""
     from td3_amd.TD3_featured import TD3
     from td3_amd.my_replay_buffer import ReplayBuffer_featured
+    fill = rows if fill is None else fill
     a0 = gen.init_params(gen._mlp_shapes("", sd, actor_arch, ad, norm), gen.SEED)
     c0 = gen.init_params(gen._mlp_shapes("q1.", sd + ad, q_arch, 1, norm) +
                          gen._mlp_shapes("q2.", sd + ad, q_arch, 1, norm), gen.SEED + 100)
     buf = orc.FeaturedBuffer(sd, ad, rows)
-    s, a, s2, r, d = gen.fill_featured_buffer(sd, ad, ma, rows, gen.SEED)
-    for i in range(rows):
+    s, a, s2, r, d = (x[:fill] for x in gen.fill_featured_buffer(sd, ad, ma, rows, gen.SEED))
+    for i in range(fill):
         buf.add(s[i], a[i], s2[i], r[i], d[i])
     pol = TD3(Box((sd,)), Box((ad,)), max_action=ma, norm=norm, actor_arch=actor_arch, q_arch=q_arch,
-              init="none")
+              init="none", use_graph=use_graph)
     pol.set_weights(a0, c0)
-    rb = ReplayBuffer_featured(Box((sd,)), Box((ad,)), max_size=rows)
+    rb = ReplayBuffer_featured(Box((sd,)), Box((ad,)), max_size=rows, seed=rb_seed)
     rb.add_batch(s, a, s2, r, d)
     L = orc.Learner(a0, c0, max_action=ma, norm=norm)
     return pol, rb, L, buf
@@ -73,6 +78,9 @@ def test_ragged_batches(B):
 def test_large_batch_dw_tiles(B):
     pol, rb, L, buf = _setup(17, 6)
     _teacher_forced(pol, rb, L, buf, B, 6, seed=B)
+    kernel = {544: "td3::dw64_kernel<true>", 640: "td3::dwsk_kernel<true, false>"}[B]
+    for phase in (0, 1):                      # a real step each: after the comparison
+        assert dict(stage_kernels(pol, rb, B, phase))["C_dw"] == kernel, phase
 
 
 @pytest.mark.parametrize("norm", ["layer", None])
