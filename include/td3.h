@@ -19,6 +19,9 @@
  *   td3_train_step_batch TD3.train on a foreign buffer's sample() tensors
  *   td3_select_action    TD3.select_action                TD3_featured.py:113-115
  *   td3_eval_q           TD3.eval_q                       TD3_featured.py:117-121
+ *   rb_add_device        ReplayBuffer_featured.add on device rows (GPU-resident environments)
+ *   td3_select_action_device  select_action + OU noise + clip on device rows  main.py:249-252, utils/noise.py
+ *   td3_eval_q_device    TD3.eval_q on device rows
  *   td3_*_particles      TD3_particles.TD3 (set encoder)  TD3_particles.py:136-224
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
  *   td3_comm_init(_local) data-parallel extension (the reference is single-device)
@@ -74,6 +77,14 @@ int rb_add(rb_handle* h, const double* state, const double* action, const double
            const double* reward, const double* done, int64_t n, void* stream);
 /* n packed float32 records (record_floats each). */
 int rb_add_records(rb_handle* h, const float* records, int64_t n, void* stream);
+/* n transitions from DEVICE float32 arrays (contiguous: state [n][sd], action [n][ad],
+ * next_state [n][sd], reward [n], done [n]) into ring rows ptr, ptr+1, ... (wrapping);
+ * stores not_done = 1.0f - done, zeroes the record pad.  n > max_size keeps the last max_size rows
+ * (as rb_add).  Asynchronous on `stream` (NULL: the ring's own); inputs must stay valid until that
+ * stream's work has completed.  The records are assembled in the ring by one kernel: no staging
+ * buffer, no host copy.  Featured rings only: the particle ring has no device add (-1). */
+int rb_add_device(rb_handle* h, const float* state, const float* action, const float* next_state,
+                  const float* reward, const float* done, int64_t n, void* stream);
 /* Device-side synthetic prefill (SURVEY.md §8d distribution), n rows at ptr. */
 int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, void* stream);
 /* Gather `batch` rows into device outputs state[B][sd], action[B][ad], next_state[B][sd],
@@ -187,6 +198,34 @@ int td3_train_step_batch(td3_handle* h, const float* state, const float* action,
 int td3_select_action(td3_handle* h, const float* state, float* action_out, int n);
 /* (state, action) (host) -> q_out[2*n] = Q1, Q2; synchronous. */
 int td3_eval_q(td3_handle* h, const float* state, const float* action, float* q_out, int n);
+
+/* Device-resident queries (featured learners only; a particle handle returns -1).  Nothing crosses the
+ * host: rows are read from and written to device memory, the call only queues work.
+ * Exploration noise applied on the device (main.py:249-252, utils/noise.py).  The N(0,1) values are
+ * Philox4x32-10 with key (seed lo, seed hi) and counter (idx, stream id, step lo, step hi), where
+ * idx = row * ceil(action_dim / 4) + column / 4 (four normals per counter) and the stream id is the
+ * exploration draw's own (4), not the one of the training step's target-policy noise (2): the same
+ * (seed, step) gives unrelated values in the two. */
+typedef struct td3_explore {
+  float* x;                       /* device [n][ad] OU state, read and written; NULL: Gaussian, a = clip(pi + sigma*z) */
+  float mu, theta, sigma;         /* X <- X + (theta*(mu - X) + sigma*z); a = clip(pi + X, -max_action, max_action) */
+  const uint8_t* reset;           /* device [n], nullable: nonzero -> X = mu before this update (episode ended) */
+  uint64_t seed, step;            /* Philox key / counter of this call's N(0,1) draw */
+  const float* inject_z;          /* device [n][ad], nullable: replaces the draw (parity testing) */
+  float* z_out;                   /* device [n][ad], nullable: receives the N(0,1) values used */
+} td3_explore;
+/* device state [n][sd] -> device action_out [n][ad]; ex NULL: the plain policy.  Any n >= 1 (the first
+ * call at a new pad32(n) builds its plan, which synchronises the device once).  Asynchronous on `stream`
+ * (NULL: the learner's step stream, so it is ordered after every queued step); no host synchronisation.
+ * A non-NULL stream is first ordered after the last queued step's stream, and after a previous device
+ * query on another stream, by an event recorded there: a caller's stream given to a step or to a
+ * device query must stay alive until the next device query or td3_destroy.  A step queued LATER on
+ * another stream is not ordered after the query: the caller orders those.  Pointers must stay valid
+ * until the stream's work has completed. */
+int td3_select_action_device(td3_handle* h, const float* state, int n, const td3_explore* ex,
+                             float* action_out, void* stream);
+/* device (state, action) -> device q_out [2][n] (Q1 then Q2); asynchronous as above. */
+int td3_eval_q_device(td3_handle* h, const float* state, const float* action, int n, float* q_out, void* stream);
 
 /* TD3_particles (TD3_particles.py:153-164, 167-224). */
 int td3_train_step_batch_particles(td3_handle* h, const float* feat, const float* part, const float* action,

@@ -331,6 +331,78 @@ class TD3(TD3_base):
         check(self._lib.td3_eval_q(self._h, _lib.fptr(s), _lib.fptr(a), _lib.fptr(q), n), "td3_eval_q")
         return q[:n].copy(), q[n:].copy()
 
+    # ------------------------------------------------------------------ device-resident queries
+    def _device_rows(self, x, cols):
+        torch = _torch()
+        return torch.as_tensor(x, device=self.device).to(torch.float32).reshape(-1, cols).contiguous()
+
+    def select_action_device(self, states, noise=None, reset=None, inject_z=None, return_z=False):
+        """``select_action`` for n device rows at once, nothing crossing the host: ``states`` (torch
+        CUDA tensor ``[n][state_dim]``) -> actions (``[n][action_dim]`` float32 on the device).
+
+        ``noise`` (``exploration.DeviceOUNoise`` / ``DeviceGaussianNoise``, or None for the plain
+        policy) is applied in the query's epilogue kernel and clipped to ``max_action``
+        (main.py:249-252); its OU state advances in place and its step counter by one.  ``reset``
+        (``[n]`` bool / uint8, nullable) returns those rows' OU state to ``mu`` first; ``inject_z``
+        (``[n][action_dim]``) replaces the N(0, 1) draw; ``return_z`` also returns the values used.
+        Queued on the learner's step stream: ordered after every queued ``train``."""
+        torch = _torch()
+        s = self._device_rows(states, self.state_dim)
+        n = s.shape[0]
+        out = torch.empty((n, self.action_dim), device=self.device, dtype=torch.float32)
+        ex, z, keep = None, None, []
+        if noise is None and (reset is not None or inject_z is not None or return_z):
+            raise ValueError("reset / inject_z / return_z need a noise process")
+        if noise is not None:
+            ex = _lib.td3_explore()
+            if noise.X is not None:
+                if tuple(noise.X.shape) != (n, self.action_dim) or noise.X.dtype != torch.float32 \
+                        or not noise.X.is_contiguous() or noise.X.device != self.device:
+                    raise ValueError(f"noise.X must be a contiguous float32 [{n}][{self.action_dim}] tensor on {self.device}")
+                ex.x = noise.X.data_ptr()
+            ex.mu, ex.theta, ex.sigma = float(noise.mu), float(noise.theta), float(noise.sigma)
+            ex.seed, ex.step = int(noise.seed), int(noise.step)
+            if reset is not None:
+                rm = torch.as_tensor(reset, device=self.device).reshape(-1)
+                if rm.dtype == torch.bool and rm.is_contiguous():
+                    rm = rm.view(torch.uint8)           # a done mask as the env returned it: no kernel
+                else:
+                    rm = (rm != 0).to(torch.uint8).contiguous()
+                if rm.shape[0] != n:
+                    raise ValueError("reset must have one entry per row")
+                keep.append(rm)
+                ex.reset = rm.data_ptr()
+            if inject_z is not None:
+                iz = self._device_rows(inject_z, self.action_dim)
+                if iz.shape[0] != n:
+                    raise ValueError("inject_z must be [n][action_dim]")
+                keep.append(iz)
+                ex.inject_z = iz.data_ptr()
+            if return_z:
+                z = torch.empty((n, self.action_dim), device=self.device, dtype=torch.float32)
+                ex.z_out = z.data_ptr()
+            noise.step += 1
+        # as train_step's foreign-buffer path: on exit torch's stream waits for the learner's, so the
+        # temporaries freed here are reused only after the query read them
+        with self._torch_order():
+            check(self._lib.td3_select_action_device(self._h, s.data_ptr(), n, C.byref(ex) if ex is not None else None,
+                                                     out.data_ptr(), self._stream()), "td3_select_action_device")
+        return (out, z) if return_z else out
+
+    def eval_q_device(self, states, actions):
+        """``eval_q`` over n device rows: (Q1 [n], Q2 [n]) float32 on the device."""
+        torch = _torch()
+        s = self._device_rows(states, self.state_dim)
+        a = self._device_rows(actions, self.action_dim)
+        if s.shape[0] != a.shape[0]:
+            raise ValueError("states and actions must have the same number of rows")
+        n = s.shape[0]
+        q = torch.empty((2, n), device=self.device, dtype=torch.float32)
+        with self._torch_order():
+            check(self._lib.td3_eval_q_device(self._h, s.data_ptr(), a.data_ptr(), n, q.data_ptr(), self._stream()),
+                  "td3_eval_q_device")
+        return q[0], q[1]
+
     def train(self, replay_buffer, batch_size=100):
         self.train_step(replay_buffer, batch_size)
 

@@ -39,6 +39,12 @@ class td3_step_stats(C.Structure):
                 ("noise", C.c_void_p)]
 
 
+class td3_explore(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("mu", C.c_float), ("theta", C.c_float), ("sigma", C.c_float),
+                ("reset", C.c_void_p), ("seed", C.c_uint64), ("step", C.c_uint64),
+                ("inject_z", C.c_void_p), ("z_out", C.c_void_p)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -52,6 +58,7 @@ SIGNATURES = {
     "rb_stream": (_P, [_P]),
     "rb_add": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int64, _P]),
     "rb_add_records": (C.c_int, [_P, _F, C.c_int64, _P]),
+    "rb_add_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rb_fill_synthetic": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     "rb_sample": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
@@ -79,6 +86,8 @@ SIGNATURES = {
                                        C.POINTER(td3_step_stats)]),
     "td3_select_action": (C.c_int, [_P, _F, _F, C.c_int]),
     "td3_eval_q": (C.c_int, [_P, _F, _F, _F, C.c_int]),
+    "td3_select_action_device": (C.c_int, [_P, _P, C.c_int, C.POINTER(td3_explore), _P, _P]),
+    "td3_eval_q_device": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
     "td3_train_step_batch_particles": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _F,
                                                  C.POINTER(td3_step_stats)]),
     "td3_actor_learn_particles": (C.c_int, [_P, _P, _P, C.c_int, _P, _D]),

@@ -69,8 +69,16 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 ctr, uint32_t k0, uint32_t 
   return ctr;
 }
 
-// Stream ids of the per-step Philox draws.
-enum : uint32_t { kStreamIndex = 1u, kStreamNoise = 2u, kStreamFill = 3u };
+// Stream ids of the per-step Philox draws.  Every draw is Philox4x32-10 with
+//   key     = (seed lo, seed hi)
+//   counter = (idx, stream id, step lo, step hi)
+// so two draws share values only when seed, step, stream id and idx all agree.  idx per stream:
+//   kStreamIndex    the batch row (philox_index: one sampled ring row per counter)
+//   kStreamNoise    row * 8 + column / 4 of the target-policy noise (four normals per counter)
+//   kStreamFill     the record column of rb_fill_synthetic (step = the row filled)
+//   kStreamExplore  row * ceil(action_dim / 4) + column / 4 of td3_select_action_device's
+//                   exploration draw (step = td3_explore::step, seed = td3_explore::seed)
+enum : uint32_t { kStreamIndex = 1u, kStreamNoise = 2u, kStreamFill = 3u, kStreamExplore = 4u };
 
 // Uniform integer in [0, n) from 64 random bits (multiply-high; bias < n / 2^64).
 __device__ __forceinline__ uint64_t philox_index(uint64_t seed, uint64_t step, uint32_t row,

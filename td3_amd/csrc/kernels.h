@@ -643,6 +643,24 @@ struct W4PackArgs {
   int nmat;
 };
 int launch_w4_pack(const W4PackArgs& a, hipStream_t s);
+// Epilogue of td3_select_action_device: the policy head's rows pi (max_action * tanh, row stride ldp)
+// -> action_out [n][ad].  plain: a copy.  Otherwise z ~ N(0,1) (Philox kStreamExplore, or inject_z),
+// x != null: the Ornstein-Uhlenbeck state X <- X + (theta (mu - X) + sigma z) (X = mu first where
+// reset[row] != 0) and a = clamp(pi + X); x == null: a = clamp(pi + sigma z).
+struct ExploreArgs {
+  const float* pi; int ldp;
+  float* action_out;
+  int n, ad;
+  int plain;
+  float max_action;
+  float* x;
+  float mu, theta, sigma;
+  const uint8_t* reset;
+  uint64_t seed, step;
+  const float* inject_z;
+  float* z_out;
+};
+int launch_explore(const ExploreArgs& a, hipStream_t s);
 int kernels_init();
 
 }  // namespace td3

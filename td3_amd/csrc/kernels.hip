@@ -3952,6 +3952,51 @@ int launch_w4_pack(const W4PackArgs& a, hipStream_t s) {
   return 0;
 }
 
+// One thread per (row, 4 action columns): the Philox counter of the quad is drawn once, the OU state
+// and the action are read and written in place (utils/noise.py:15-19 order: drift, + diffusion, + X).
+__global__ __launch_bounds__(256) void explore_kernel(ExploreArgs a) {
+  const int ad4 = (a.ad + 3) >> 2;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)a.n * ad4) return;
+  const int row = (int)(t / ad4), q = (int)(t - (int64_t)row * ad4);
+  const float* pi = a.pi + (size_t)row * a.ldp;
+  const size_t o = (size_t)row * a.ad;
+  if (a.plain) {
+    for (int c = 4 * q; c < min(4 * q + 4, a.ad); ++c) a.action_out[o + c] = pi[c];
+    return;
+  }
+  float z[4];
+  if (!a.inject_z) philox_normal4(a.seed, a.step, kStreamExplore, (uint32_t)t, z);
+  const bool rst = a.reset && a.reset[row] != 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = 4 * q + j;
+    if (c >= a.ad) break;
+    const float zz = a.inject_z ? a.inject_z[o + c] : z[j];
+    float e;
+    if (a.x) {
+      const float X = rst ? a.mu : a.x[o + c];
+      e = X + (a.theta * (a.mu - X) + a.sigma * zz);
+      a.x[o + c] = e;
+    } else {
+      e = a.sigma * zz;
+    }
+    if (a.z_out) a.z_out[o + c] = zz;
+    a.action_out[o + c] = fminf(fmaxf(pi[c] + e, -a.max_action), a.max_action);
+  }
+}
+
+int launch_explore(const ExploreArgs& a, hipStream_t s) {
+  if (a.n < 1 || a.ad < 1 || !a.pi || !a.action_out) {
+    set_error("launch_explore: %d rows x %d columns", a.n, a.ad);
+    return -1;
+  }
+  const int64_t threads = (int64_t)a.n * ((a.ad + 3) >> 2);
+  hipLaunchKernelGGL(explore_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  return 0;
+}
+
 // Polyak over a whole arena (the sharded data-parallel step, behind its all-gather) that also
 // refreshes the k-quad images of the weight matrices from the gathered P and the new T (w.base = 0)
 __global__ __launch_bounds__(256) void polyak_w4_kernel(float* T, const float* P, int64_t n, float tau, float omt,

@@ -2,7 +2,8 @@
 //
 // Reference: /root/reference/my_replay_buffer.py
 //   ReplayBuffer_featured.__init__  :73-89   -> rb_create
-//   ReplayBuffer_featured.add       :109-117 -> rb_add (batched, pinned staging, async H2D)
+//   ReplayBuffer_featured.add       :109-117 -> rb_add (batched, pinned staging, async H2D),
+//                                               rb_add_device (device rows, records built in the ring)
 //   ReplayBuffer_featured.sample    :119-128 -> rb_sample / gather_kernel (Philox + HBM gather)
 //   ReplayBuffer_featured.save/load :91-107  -> rb_read_records / rb_write_records
 //   ReplayBuffer_particles          :6-69    -> rb_create_particles / rb_add_particles /
@@ -166,6 +167,39 @@ __global__ __launch_bounds__(256) void ring_put_args_kernel(RingPutArgs a) {
     a.data[dst * a.rec4 + c] = reinterpret_cast<const float4*>(a.rows)[i];
   }
   if (threadIdx.x == 0) *a.d_size = a.new_size;
+}
+
+// Adds from device arrays (rb_add_device): the records [s | a | s' | r | not_done | pad] are assembled
+// in the ring itself, one thread per float4 of a record.  Consecutive threads walk a record's columns
+// and then the next row's, so each source array is read in order (row-major, unit stride inside a
+// segment); source row `skip + row` goes to ring row ptr + row (wrapping once: n <= cap).
+struct RingPutDeviceArgs {
+  float4* data;
+  int64_t* d_size;
+  const float *state, *action, *next_state, *reward, *done;
+  int64_t cap, ptr, n, skip, new_size;
+  int sd, ad, o_s2, o_r, o_nd, rec4;
+};
+__device__ __forceinline__ float ring_put_device_elem(const RingPutDeviceArgs& a, int64_t r, int c) {
+  if (c < a.sd) return a.state[r * a.sd + c];
+  if (c < a.o_s2) return a.action[r * a.ad + (c - a.sd)];
+  if (c < a.o_r) return a.next_state[r * a.sd + (c - a.o_s2)];
+  if (c == a.o_r) return a.reward[r];
+  if (c == a.o_nd) return 1.0f - a.done[r];               // my_replay_buffer.py:114
+  return 0.f;                                             // record pad
+}
+__global__ __launch_bounds__(256) void ring_put_device_kernel(RingPutDeviceArgs a) {
+  const int64_t total = a.n * a.rec4;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / a.rec4;
+    const int c = (int)(i - row * a.rec4) * 4;
+    const int64_t r = a.skip + row;
+    int64_t dst = a.ptr + row;
+    if (dst >= a.cap) dst -= a.cap;
+    a.data[dst * a.rec4 + (c >> 2)] = make_float4(ring_put_device_elem(a, r, c), ring_put_device_elem(a, r, c + 1),
+                                                  ring_put_device_elem(a, r, c + 2), ring_put_device_elem(a, r, c + 3));
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *a.d_size = a.new_size;
 }
 
 // The lazy ordering of Ring::read_stream / write_stream: when `s` differs from the noted stream,
@@ -511,6 +545,52 @@ int rb_add_records(rb_handle* h, const float* records, int64_t n, void* stream) 
   if (!stage) return -2;
   memcpy(stage, records, (size_t)n * r->rec * sizeof(float));
   return push_staged(r, stage, n, s);
+}
+
+int rb_add_device(rb_handle* h, const float* state, const float* action, const float* next_state,
+                  const float* reward, const float* done, int64_t n, void* stream) {
+  TD3_ARG(n >= 0, "n must be >= 0");
+  TD3_ARG(h != nullptr, "null handle");
+  if (n == 0) return 0;
+  TD3_ARG(state && action && next_state && reward && done, "null input");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(!r->particles, "rb_add_device on a particle ring (particle rings have no device add)");
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_write(r, s));
+  // ptr / size as push_staged: only the last `cap` rows survive when n > cap
+  RingPutDeviceArgs a{};
+  if (n > r->cap) {
+    a.skip = n - r->cap;
+    r->ptr = (r->ptr + a.skip) % r->cap;
+    n = r->cap;
+    r->size = r->cap;
+  }
+  const int64_t new_size = std::min<int64_t>(r->size + n, r->cap);
+  a.data = reinterpret_cast<float4*>(r->data);
+  a.d_size = r->d_size;
+  a.state = state;
+  a.action = action;
+  a.next_state = next_state;
+  a.reward = reward;
+  a.done = done;
+  a.cap = r->cap;
+  a.ptr = r->ptr;
+  a.n = n;
+  a.new_size = new_size;
+  a.sd = r->sd;
+  a.ad = r->ad;
+  a.o_s2 = r->o_s2;
+  a.o_r = r->o_r;
+  a.o_nd = r->o_nd;
+  a.rec4 = r->rec / 4;
+  const int64_t total4 = n * a.rec4;
+  const int grid = (int)std::min<int64_t>((total4 + 255) / 256, 1024);
+  hipLaunchKernelGGL(ring_put_device_kernel, dim3(grid), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  r->ptr = (r->ptr + n) % r->cap;
+  r->size = new_size;
+  return ring_end_write(r, s);
 }
 
 int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, void* stream) {

@@ -5,7 +5,9 @@
 //   TD3_featured.TD3.train      :123-171  -> td3_train_step (the stage list built by build_step)
 //   TD3_featured.TD3.select_action :113-115 -> td3_select_action
 //   TD3_featured.TD3.eval_q     :117-121  -> td3_eval_q
-//   TD3_base save/load          TD3_base.py:26-50 -> td3_get_params / td3_set_params
+//   main.py:249-252 (select_action + OU noise + clip) on device rows -> td3_select_action_device;
+//   eval_q on device rows -> td3_eval_q_device (asynchronous, nothing crosses the host)
+//   TD3_base save/load         TD3_base.py:26-50 -> td3_get_params / td3_set_params
 //
 // HBM layout
 //   * one fp32 arena per parameter group (actor: 1 MLP; critic: q1 then q2), five
@@ -374,6 +376,13 @@ struct td3_handle {
   hipStream_t last_step_stream = nullptr;     // the stream of the last train step
   std::unique_ptr<Plan> plan;
   std::map<int, std::unique_ptr<ActPlan>> act;
+  // Device-resident queries (td3_select_action_device / td3_eval_q_device) run asynchronously on the
+  // step stream or a caller's: plans of their own (device I/O only), so a query still in flight never
+  // shares scratch with a synchronous host query on the acting stream.  dev_stream: the stream of the
+  // last one; a query on another stream waits for dev_ev recorded there (same scratch).
+  std::map<int, std::unique_ptr<ActPlan>> act_dev;
+  hipStream_t dev_stream = nullptr;
+  hipEvent_t dev_ev = nullptr;
   ncclComm_t comm = nullptr;
   // the overlapped data-parallel schedule (add_dw_stage buckets): the all-reduces and the per-bucket
   // optimizer steps run on comm_stream, ordered after the bucket's dW by comm_ev (recorded on the step
@@ -2504,9 +2513,12 @@ static int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_s
 // ------------------------------------------------------------------ act / eval_q plans
 // select_action / eval_q of <= kGemvRows rows as one act_kernel launch (TD3_ACT1=1, the default) or
 // the gemv01 -> gemv -> head chain of three launches (0: the A/B reference; read when a plan is built)
-static int build_act(td3_handle* h, int Bp, ActPlan** out) {
-  auto it = h->act.find(Bp);
-  if (it != h->act.end()) {
+// dev: a plan of the device-resident queries (td3_handle::act_dev): inputs and outputs in device
+// scratch at every size (no mapped block, so no one-launch query either: the stage lists run).
+static int build_act(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
+  auto& plans = dev ? h->act_dev : h->act;
+  auto it = plans.find(Bp);
+  if (it != plans.end()) {
     *out = it->second.get();
     return 0;
   }
@@ -2524,7 +2536,7 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out) {
   TD3_HIP(hipDeviceSynchronize());
   Scratch S{A->scratch, floats, 0};
   IoCarve io{&S};
-  TD3_RC(map_io(A.get(), io_floats, &io));
+  if (!dev) TD3_RC(map_io(A.get(), io_floats, &io));
   A->X_S = io.take((size_t)Bp * lds_s, &A->hX_S);
   A->X_SA = io.take((size_t)Bp * lds_sa, &A->hX_SA);
   A->out = io.take((size_t)Bp * h->ad, &A->hout);
@@ -2662,7 +2674,7 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out) {
     }
   }
   *out = A.get();
-  h->act[Bp] = std::move(A);
+  plans[Bp] = std::move(A);
   return 0;
 }
 
@@ -2958,11 +2970,15 @@ int td3_destroy(td3_handle* h) {
   (void)hipStreamSynchronize(h->act_stream);
   ring_forget_stream(h->stream);        // rings that noted it as their reader / writer
   if (h->plan) destroy_plan(h->plan.get());
-  for (auto& kv : h->act) {
-    free_plan_tables(kv.second->tables);
-    (void)hipFree(kv.second->scratch);
-    if (kv.second->hio) (void)hipHostFree(kv.second->hio);
-  }
+  // a device-resident query on a caller's stream may still read its plan and the parameters
+  if (h->dev_stream && h->dev_stream != h->stream) (void)hipStreamSynchronize(h->dev_stream);
+  if (h->dev_ev) (void)hipEventDestroy(h->dev_ev);
+  for (auto* plans : {&h->act, &h->act_dev})
+    for (auto& kv : *plans) {
+      free_plan_tables(kv.second->tables);
+      (void)hipFree(kv.second->scratch);
+      if (kv.second->hio) (void)hipHostFree(kv.second->hio);
+    }
   if (h->comm_stream) {
     (void)hipStreamSynchronize(h->comm_stream);
     (void)hipStreamDestroy(h->comm_stream);
@@ -3417,6 +3433,83 @@ int td3_eval_q(td3_handle* h, const float* state, const float* action, float* q_
   if (A->hio) TD3_HIP(hipStreamSynchronize(s));
   TD3_RC(get_rows(q_out, 1, A->q[0], A->hq[0], 1, n, s));
   return get_rows(q_out + n, 1, A->q[1], A->hq[1], 1, n, s);
+}
+
+// ------------------------------------------------------------------ device-resident queries
+// The stream a device query runs on, ordered by events where stream order does not already do it:
+// after the last queued step (the parameters it may still update) and after a previous device query
+// on another stream (the act_dev plans' scratch).  NULL is the step stream itself.
+static int device_query_stream(td3_handle* h, void* stream, hipStream_t* out) {
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  if (!h->dev_ev) TD3_HIP(hipEventCreateWithFlags(&h->dev_ev, TD3_EV_FLAGS));
+  for (hipStream_t prev : {h->last_step_stream, h->dev_stream}) {
+    if (!prev || prev == s) continue;
+    TD3_HIP(hipEventRecord(h->dev_ev, prev));
+    TD3_HIP(hipStreamWaitEvent(s, h->dev_ev, 0));
+  }
+  h->dev_stream = s;
+  *out = s;
+  return 0;
+}
+
+int td3_select_action_device(td3_handle* h, const float* state, int n, const td3_explore* ex,
+                             float* action_out, void* stream) {
+  TD3_ARG(n > 0, "n must be positive");
+  TD3_ARG(h && state && action_out, "null argument");
+  TD3_ARG(!h->particles, "particle learner: no device-resident query (use td3_select_action_particles)");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  const int Bp = pad32(n);
+  ActPlan* A;
+  TD3_RC(build_act(h, Bp, &A, true));
+  hipStream_t s;
+  TD3_RC(device_query_stream(h, stream, &s));
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, state, h->sd, n, Bp, A->X_S, pad32(h->sd), 0,
+                     (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
+  TD3_HIP(hipGetLastError());
+  TD3_RC(run_stages(A->act, s));
+  ExploreArgs e{};
+  e.pi = A->out;
+  e.ldp = A->ldo;
+  e.action_out = action_out;
+  e.n = n;
+  e.ad = h->ad;
+  e.plain = ex ? 0 : 1;
+  e.max_action = h->cfg.max_action;
+  if (ex) {
+    e.x = ex->x;
+    e.mu = ex->mu;
+    e.theta = ex->theta;
+    e.sigma = ex->sigma;
+    e.reset = ex->reset;
+    e.seed = ex->seed;
+    e.step = ex->step;
+    e.inject_z = ex->inject_z;
+    e.z_out = ex->z_out;
+  }
+  return launch_explore(e, s);
+}
+
+int td3_eval_q_device(td3_handle* h, const float* state, const float* action, int n, float* q_out, void* stream) {
+  TD3_ARG(n > 0, "n must be positive");
+  TD3_ARG(h && state && action && q_out, "null argument");
+  TD3_ARG(!h->particles, "particle learner: no device-resident query (use td3_eval_q_particles)");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  const int Bp = pad32(n), ld = pad32(h->sd + h->ad);
+  ActPlan* A;
+  TD3_RC(build_act(h, Bp, &A, true));
+  hipStream_t s;
+  TD3_RC(device_query_stream(h, stream, &s));
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, state, h->sd, n, Bp, A->X_SA, ld, 0,
+                     (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, action, h->ad, n, Bp, A->X_SA, ld, h->sd,
+                     (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
+  TD3_HIP(hipGetLastError());
+  TD3_RC(run_stages(A->evalq, s));
+  for (int j = 0; j < 2; ++j)        // the live rows of Q_j -> q_out[j][0..n)
+    hipLaunchKernelGGL(pack_kernel, dim3(n), dim3(64), 0, s, A->q[j], 1, n, n, q_out + (size_t)j * n, 1, 0,
+                       (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
+  TD3_HIP(hipGetLastError());
+  return 0;
 }
 
 int td3_train_step_batch_particles(td3_handle* h, const float* feat, const float* part, const float* action,

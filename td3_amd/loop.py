@@ -21,6 +21,11 @@ What runs where on MI355X:
 The gym / MuJoCo / SPlisHSPlasH environments are not part of this build (not installed here);
 ``SyntheticEnv`` is a gym-shaped stand-in with a configurable host cost per step, used by
 ``bench.py --loop`` and the tests.
+
+``DeviceTrainLoop`` is the same order for environments that live on the GPU (``SyntheticVecEnv``:
+the stand-in as torch ops on ``[n_envs]`` device rows): ``select_action_device`` applies policy,
+OU noise and clip on the device, ``add_batch`` on CUDA tensors assembles the ring records from
+device memory, and no transition crosses the host (``tools/bench_rollout.py``).
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ import numpy as np
 
 from .exploration import OrnsteinUhlenbeckActionNoise
 
-__all__ = ["add_to_replay_buffer", "TrainLoop", "SyntheticEnv", "Box"]
+__all__ = ["add_to_replay_buffer", "TrainLoop", "SyntheticEnv", "Box", "SyntheticVecEnv", "DeviceTrainLoop"]
 
 
 def add_to_replay_buffer(replay_buffer, state, action, reward, next_state, done_bool, relabels=()):
@@ -149,3 +154,103 @@ class TrainLoop:
         dt = time.perf_counter() - t0
         return {"env_steps": int(max_timesteps), "grad_steps": grad_steps, "episodes": episode_num,
                 "seconds": dt, "env_steps_per_s": int(max_timesteps) / dt if dt > 0 else 0.0}
+
+
+class SyntheticVecEnv:
+    """``n_envs`` copies of ``SyntheticEnv``'s dynamics as torch ops on device rows (a stand-in for a
+    batched GPU simulator): s' = tanh(s W^T + a U^T), r = -|s'|^2 / sd, episodes of fixed length,
+    fp32.  Finished rows reset themselves: ``step`` returns the transition's own
+    ``(next_state, reward, done, time_limit)`` (``time_limit``: the episode ended at
+    ``max_episode_steps``, main.py:256's done swap) while ``state`` already holds the observation
+    the next action is chosen from, i.e. the fresh one on the rows that ended."""
+
+    def __init__(self, n_envs, state_dim, action_dim, max_action=1.0, max_episode_steps=1000, seed=0,
+                 device=None):
+        import torch
+        rs = np.random.RandomState(seed)
+        self.n_envs = int(n_envs)
+        self.observation_space = Box(-np.inf, np.inf, (state_dim,))
+        self.action_space = Box(-max_action, max_action, (action_dim,))
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        W = rs.standard_normal((state_dim, state_dim)) / np.sqrt(state_dim)
+        U = rs.standard_normal((state_dim, action_dim)) / np.sqrt(action_dim)
+        self._Wt = torch.as_tensor(W.T.copy(), dtype=torch.float32, device=self.device)
+        self._Ut = torch.as_tensor(U.T.copy(), dtype=torch.float32, device=self.device)
+        self._max_episode_steps = int(max_episode_steps)
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+        self._t = torch.zeros(self.n_envs, dtype=torch.int64, device=self.device)
+        self.state = None
+
+    def _fresh(self):
+        import torch
+        return 0.1 * torch.randn((self.n_envs, self._Wt.shape[0]), generator=self._gen, device=self.device,
+                                 dtype=torch.float32)
+
+    def reset(self):
+        self._t.zero_()
+        self.state = self._fresh()
+        return self.state
+
+    def step(self, action):
+        import torch
+        nxt = torch.tanh(self.state @ self._Wt + action.to(torch.float32) @ self._Ut)
+        reward = -(nxt * nxt).sum(dim=1) / nxt.shape[1]
+        self._t += 1
+        done = self._t >= self._max_episode_steps
+        self.state = torch.where(done[:, None], self._fresh(), nxt)
+        self._t.masked_fill_(done, 0)
+        return nxt, reward, done, done.clone()
+
+
+class DeviceTrainLoop:
+    """``main.py:240-289``'s order per tick over all rows of a GPU-resident vector environment
+    (``state`` attribute, ``reset()``, ``step(actions) -> (next_state, reward, done, time_limit)``
+    on device tensors, auto-reset as ``SyntheticVecEnv``): act (uniform before ``start_policy``
+    ticks, else the policy with device OU noise), ``env.step``, ``add_batch`` of the n transitions,
+    ``train_steps_per_tick`` gradient steps from tick ``start_training`` on; rows whose episode
+    ended have their noise reset at the next query.  Every piece only queues GPU work
+    (``select_action_device``, ``rb_add_device``, ``train``): the host reads nothing back and
+    keeps only the tick counter."""
+
+    def __init__(self, env, policy, replay_buffer, *, start_policy, start_training, batch_size, expl_noise,
+                 done_swap=True, train_steps_per_tick=1, seed=0):
+        from .exploration import DeviceOUNoise
+        self.env, self.policy, self.replay_buffer = env, policy, replay_buffer
+        self.start_policy, self.start_training = int(start_policy), int(start_training)
+        self.batch_size = int(batch_size)
+        self.done_swap = done_swap
+        self.train_steps_per_tick = int(train_steps_per_tick)
+        self.max_action = float(policy.max_action)
+        self.noise = DeviceOUNoise(env.n_envs, policy.action_dim, sigma=expl_noise, device=policy.device,
+                                   seed=seed)
+
+    def run(self, max_ticks):
+        import torch
+        env, policy, rb = self.env, self.policy, self.replay_buffer
+        n, ad, ma = env.n_envs, policy.action_dim, self.max_action
+        state = env.reset()
+        ended = None                          # rows whose episode ended at the previous tick
+        grad_steps = 0
+        t0 = time.perf_counter()
+        for t in range(int(max_ticks)):
+            if t < self.start_policy:
+                action = (torch.rand((n, ad), device=state.device, dtype=torch.float32) * 2 - 1) * ma
+                if ended is not None:
+                    self.noise.reset(ended)
+            else:
+                action = policy.select_action_device(state, noise=self.noise, reset=ended)
+            next_state, reward, done, time_limit = env.step(action)
+            done_bool = (done & ~time_limit) if self.done_swap else done
+            rb.add_batch(state, action, next_state, reward, done_bool)
+            state, ended = env.state, done
+            if t >= self.start_training:
+                for _ in range(self.train_steps_per_tick):
+                    policy.train(rb, self.batch_size)
+                    grad_steps += 1
+        policy.sync()
+        torch.cuda.synchronize(state.device)
+        dt = time.perf_counter() - t0
+        steps = int(max_ticks) * n
+        return {"ticks": int(max_ticks), "env_steps": steps, "grad_steps": grad_steps, "seconds": dt,
+                "env_steps_per_s": steps / dt if dt > 0 else 0.0}

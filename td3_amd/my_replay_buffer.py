@@ -50,6 +50,11 @@ def default_device_index() -> int:
     return torch.cuda.current_device()
 
 
+def _is_cuda_tensor(x) -> bool:
+    """A torch tensor on a GPU (without importing torch for numpy callers)."""
+    return bool(getattr(x, "is_cuda", False))
+
+
 def _new_stage(buf, rows):
     """Host records staged by ``add`` (zeroed: the record pad stays 0) and their float*."""
     buf._stage = np.zeros((rows, buf.record_floats), dtype=np.float32)
@@ -232,8 +237,13 @@ class ReplayBuffer_featured(object):
             self.flush()
 
     def add_batch(self, state, action, next_state, reward, done):
-        """Bulk add of n transitions (experience_injection.py / hindsight relabel path)."""
+        """Bulk add of n transitions (experience_injection.py / hindsight relabel path).  Torch
+        CUDA tensors (a GPU-resident environment's rows, any float dtype) go from device memory
+        straight into the ring (``rb_add_device``): no host copy, no synchronisation."""
         self.flush()
+        if _is_cuda_tensor(state):
+            self._add_batch_device(state, action, next_state, reward, done)
+            return
         s = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, self.state_dim)
         n = s.shape[0]
         a = np.ascontiguousarray(action, dtype=np.float64).reshape(n, self.action_dim)
@@ -244,6 +254,28 @@ class ReplayBuffer_featured(object):
             self._shadow.put_batch((s, a, s2, r, 1. - d), n)
         check(self._lib.rb_add(self._h, _lib.dptr(s), _lib.dptr(a), _lib.dptr(s2), _lib.dptr(r),
                                _lib.dptr(d), n, self._stream()), "rb_add")
+
+    def _add_batch_device(self, state, action, next_state, reward, done):
+        torch = _torch()
+        dev = self.device
+
+        def rows(x, cols):
+            x = torch.as_tensor(x, device=dev).to(torch.float32)
+            return x.reshape(-1, cols).contiguous() if cols else x.reshape(-1).contiguous()
+
+        s = rows(state, self.state_dim)
+        n = s.shape[0]
+        a, s2 = rows(action, self.action_dim), rows(next_state, self.state_dim)
+        r, d = rows(reward, 0), rows(done, 0)
+        if not (a.shape[0] == s2.shape[0] == r.shape[0] == d.shape[0] == n):
+            raise ValueError("add_batch: the five inputs must have the same number of rows")
+        if self._shadow is not None:
+            self._shadow.valid = False           # rows the host never saw: save() writes the ring
+        # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
+        # the blocks freed with them are reused only after the add read them
+        with self._torch_order():
+            check(self._lib.rb_add_device(self._h, s.data_ptr(), a.data_ptr(), s2.data_ptr(), r.data_ptr(),
+                                          d.data_ptr(), n, self._stream()), "rb_add_device")
 
     def flush(self, stream=None):
         _flush_stage(self, stream)
