@@ -23,6 +23,9 @@
  *   td3_select_action_device  select_action + OU noise + clip on device rows  main.py:249-252, utils/noise.py
  *   td3_eval_q_device    TD3.eval_q on device rows
  *   td3_*_particles      TD3_particles.TD3 (set encoder)  TD3_particles.py:136-224
+ *   rb_add_particles_device   ReplayBuffer_particles.add on device rows  my_replay_buffer.py:46-56
+ *   td3_select_action_particles_device / td3_eval_q_particles_device
+ *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
  *   td3_comm_init(_local) data-parallel extension (the reference is single-device)
  *
@@ -82,7 +85,7 @@ int rb_add_records(rb_handle* h, const float* records, int64_t n, void* stream);
  * stores not_done = 1.0f - done, zeroes the record pad.  n > max_size keeps the last max_size rows
  * (as rb_add).  Asynchronous on `stream` (NULL: the ring's own); inputs must stay valid until that
  * stream's work has completed.  The records are assembled in the ring by one kernel: no staging
- * buffer, no host copy.  Featured rings only: the particle ring has no device add (-1). */
+ * buffer, no host copy.  Featured rings only: a particle ring returns -1 (rb_add_particles_device). */
 int rb_add_device(rb_handle* h, const float* state, const float* action, const float* next_state,
                   const float* reward, const float* done, int64_t n, void* stream);
 /* Device-side synthetic prefill (SURVEY.md §8d distribution), n rows at ptr. */
@@ -106,6 +109,17 @@ int rb_create_particles(int feat_dim, int n_particles, int particle_dim, int act
 int rb_add_particles(rb_handle* h, const double* feat, const double* part, const double* action,
                      const double* next_feat, const double* next_part, const double* reward,
                      const double* done, int64_t n, void* stream);
+/* rb_add_particles from DEVICE float32 arrays (contiguous: feat / next_feat [n][F], part / next_part
+ * [n][N*D], action [n][A], reward [n], done [n]): the records [feat | particles | action | next_feat |
+ * next_particles | r | not_done | pad] are assembled in ring rows ptr, ptr+1, ... (wrapping) by one
+ * kernel, with not_done = 1.0f - done and a zeroed pad; ptr / size and n > max_size as rb_add_device.
+ * The source rows need no alignment (N*D may be odd): every source float is read once, the ring is
+ * written with aligned 16-byte stores.  Asynchronous on `stream` (NULL: the ring's own), no staging
+ * buffer, no host copy; inputs must stay valid until that stream's work has completed.  A featured
+ * ring returns -1 (rb_add_device). */
+int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, const float* action,
+                            const float* next_feat, const float* next_part, const float* reward,
+                            const float* done, int64_t n, void* stream);
 /* The 7 tensors of ReplayBuffer_particles.sample (:58-69) into device outputs. */
 int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float* action, float* next_feat,
                         float* next_part, float* reward, float* not_done, const int64_t* inject_idx,
@@ -199,7 +213,8 @@ int td3_select_action(td3_handle* h, const float* state, float* action_out, int 
 /* (state, action) (host) -> q_out[2*n] = Q1, Q2; synchronous. */
 int td3_eval_q(td3_handle* h, const float* state, const float* action, float* q_out, int n);
 
-/* Device-resident queries (featured learners only; a particle handle returns -1).  Nothing crosses the
+/* Device-resident queries (these two: featured learners; a particle handle returns -1 and has
+ * td3_select_action_particles_device / td3_eval_q_particles_device below).  Nothing crosses the
  * host: rows are read from and written to device memory, the call only queues work.
  * Exploration noise applied on the device (main.py:249-252, utils/noise.py).  The N(0,1) values are
  * Philox4x32-10 with key (seed lo, seed hi) and counter (idx, stream id, step lo, step hi), where
@@ -244,6 +259,17 @@ int td3_select_action_particles(td3_handle* h, const float* feat, const float* p
 /* -> q_out [2][n][A] (Q1, then Q2; Q2 = Q1 when CDQ is off) */
 int td3_eval_q_particles(td3_handle* h, const float* feat, const float* part, const float* action, float* q_out,
                          int n);
+/* The same two queries on DEVICE rows (feat [n][F], part [n][N*D], action [n][A], all contiguous
+ * float32), asynchronous and ordered exactly as td3_select_action_device (stream, events, plan per
+ * pad32(n), any n >= 1).  The particle rows are not copied: the encoder reads `part` in place, and
+ * nothing outside [n][N*D] is read.  A featured handle returns -1.
+ * select: action_out [n][A] = clip(tanh policy + noise, -max_action, max_action) with `ex` as for
+ * td3_select_action_device (same td3_explore, same Philox stream id); ex NULL: the plain tanh policy. */
+int td3_select_action_particles_device(td3_handle* h, const float* feat, const float* part, int n,
+                                       const td3_explore* ex, float* action_out, void* stream);
+/* -> device q_out [2][n][A]: Q1 then Q2; Q2 = Q1 without CDQ. */
+int td3_eval_q_particles_device(td3_handle* h, const float* feat, const float* part, const float* action,
+                                int n, float* q_out, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL) */
 int td3_comm_unique_id(unsigned char out[128]);

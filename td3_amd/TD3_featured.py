@@ -350,6 +350,20 @@ class TD3(TD3_base):
         s = self._device_rows(states, self.state_dim)
         n = s.shape[0]
         out = torch.empty((n, self.action_dim), device=self.device, dtype=torch.float32)
+        ex, z, keep = self._explore_args(n, noise, reset, inject_z, return_z)
+        # as train_step's foreign-buffer path: on exit torch's stream waits for the learner's, so the
+        # temporaries freed here are reused only after the query read them
+        with self._torch_order():
+            check(self._lib.td3_select_action_device(self._h, s.data_ptr(), n, C.byref(ex) if ex is not None else None,
+                                                     out.data_ptr(), self._stream()), "td3_select_action_device")
+        del keep
+        return (out, z) if return_z else out
+
+    def _explore_args(self, n, noise, reset, inject_z, return_z):
+        """The ``td3_explore`` of one device policy query over n rows (None for the plain policy),
+        the tensor that receives the N(0, 1) values (``return_z``) and the temporaries the struct
+        points into, to be kept until the call is queued.  Advances ``noise.step``."""
+        torch = _torch()
         ex, z, keep = None, None, []
         if noise is None and (reset is not None or inject_z is not None or return_z):
             raise ValueError("reset / inject_z / return_z need a noise process")
@@ -382,12 +396,7 @@ class TD3(TD3_base):
                 z = torch.empty((n, self.action_dim), device=self.device, dtype=torch.float32)
                 ex.z_out = z.data_ptr()
             noise.step += 1
-        # as train_step's foreign-buffer path: on exit torch's stream waits for the learner's, so the
-        # temporaries freed here are reused only after the query read them
-        with self._torch_order():
-            check(self._lib.td3_select_action_device(self._h, s.data_ptr(), n, C.byref(ex) if ex is not None else None,
-                                                     out.data_ptr(), self._stream()), "td3_select_action_device")
-        return (out, z) if return_z else out
+        return ex, z, keep
 
     def eval_q_device(self, states, actions):
         """``eval_q`` over n device rows: (Q1 [n], Q2 [n]) float32 on the device."""

@@ -170,6 +170,60 @@ class TD3(_FeaturedTD3):
                                              _lib.fptr(q), 1), "td3_eval_q_particles")
         return [q[0].copy(), q[1].copy()] if self.CDQ else [q[0].copy()]
 
+    def eval_q_batch(self, states, actions):
+        """``eval_q`` over n host states at once: ``[Q1, Q2]`` (``[Q1]`` without CDQ), each [n][A]."""
+        feat, part = self._state_arrays(states)
+        n, A = feat.shape[0], self.action_dim
+        a = np.ascontiguousarray(np.asarray(actions, dtype=np.float32).reshape(n, A))
+        q = np.empty((2, n, A), dtype=np.float32)
+        check(self._lib.td3_eval_q_particles(self._h, _lib.fptr(feat), _lib.fptr(part), _lib.fptr(a),
+                                             _lib.fptr(q), n), "td3_eval_q_particles")
+        return [q[0].copy(), q[1].copy()] if self.CDQ else [q[0].copy()]
+
+    # ------------------------------------------------------------------ device-resident queries
+    def _device_state(self, states):
+        """(features [n][F], particles [n][N*D]) as contiguous float32 device rows; tensors that
+        already are (a GPU simulator's own buffers) pass through without a copy."""
+        f = self._device_rows(states[0], self.feat_dim)
+        p = self._device_rows(states[1], self.n_particles * self.particle_dim)
+        if f.shape[0] != p.shape[0]:
+            raise ValueError(f"features have {f.shape[0]} rows, particles {p.shape[0]}")
+        return f, p
+
+    def select_action_device(self, states, noise=None, reset=None, inject_z=None, return_z=False):
+        """``select_action`` for n device states at once, nothing crossing the host: ``states`` is
+        the tuple (features ``[n][F]``, particles ``[n][N][D]``) of torch CUDA tensors -> actions
+        (``[n][A]`` float32 on the device).  The encoder reads the particle tensor where it is.
+        ``noise`` / ``reset`` / ``inject_z`` / ``return_z`` as ``TD3_featured.TD3.select_action_device``:
+        a = clip(tanh policy + noise, -max_action, max_action) in the query's epilogue kernel."""
+        torch = _torch()
+        f, p = self._device_state(states)
+        n = f.shape[0]
+        out = torch.empty((n, self.action_dim), device=self.device, dtype=torch.float32)
+        ex, z, keep = self._explore_args(n, noise, reset, inject_z, return_z)
+        with self._torch_order():
+            check(self._lib.td3_select_action_particles_device(
+                self._h, f.data_ptr(), p.data_ptr(), n, C.byref(ex) if ex is not None else None,
+                out.data_ptr(), self._stream()), "td3_select_action_particles_device")
+        del keep
+        return (out, z) if return_z else out
+
+    def eval_q_device(self, states, actions):
+        """``eval_q`` over n device states: ``[Q1, Q2]`` (``[Q1]`` without CDQ), each ``[n][A]``
+        float32 on the device."""
+        torch = _torch()
+        f, p = self._device_state(states)
+        a = self._device_rows(actions, self.action_dim)
+        n = f.shape[0]
+        if a.shape[0] != n:
+            raise ValueError("states and actions must have the same number of rows")
+        q = torch.empty((2, n, self.action_dim), device=self.device, dtype=torch.float32)
+        with self._torch_order():
+            check(self._lib.td3_eval_q_particles_device(self._h, f.data_ptr(), p.data_ptr(), a.data_ptr(), n,
+                                                        q.data_ptr(), self._stream()),
+                  "td3_eval_q_particles_device")
+        return [q[0], q[1]] if self.CDQ else [q[0]]
+
     def _actor_learn(self, state_features, state_particles, stats=False):
         """TD3_particles.py:209-224: the delayed policy update on the given states (torch tensors or
         arrays, [B, F] and [B, N, D]), as ``evaluate_model.py:39-49`` calls it outside ``train``:

@@ -59,6 +59,7 @@ SIGNATURES = {
     "rb_add": (C.c_int, [_P, _D, _D, _D, _D, _D, C.c_int64, _P]),
     "rb_add_records": (C.c_int, [_P, _F, C.c_int64, _P]),
     "rb_add_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rb_add_particles_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rb_fill_synthetic": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     "rb_sample": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
@@ -88,6 +89,8 @@ SIGNATURES = {
     "td3_eval_q": (C.c_int, [_P, _F, _F, _F, C.c_int]),
     "td3_select_action_device": (C.c_int, [_P, _P, C.c_int, C.POINTER(td3_explore), _P, _P]),
     "td3_eval_q_device": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+    "td3_select_action_particles_device": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(td3_explore), _P, _P]),
+    "td3_eval_q_particles_device": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
     "td3_train_step_batch_particles": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _F,
                                                  C.POINTER(td3_step_stats)]),
     "td3_actor_learn_particles": (C.c_int, [_P, _P, _P, C.c_int, _P, _D]),

@@ -7,7 +7,8 @@
 //   ReplayBuffer_featured.sample    :119-128 -> rb_sample / gather_kernel (Philox + HBM gather)
 //   ReplayBuffer_featured.save/load :91-107  -> rb_read_records / rb_write_records
 //   ReplayBuffer_particles          :6-69    -> rb_create_particles / rb_add_particles /
-//                                               rb_sample_particles (same ring, wider record)
+//                                               rb_sample_particles (same ring, wider record),
+//                                               rb_add_particles_device (device rows)
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -200,6 +201,67 @@ __global__ __launch_bounds__(256) void ring_put_device_kernel(RingPutDeviceArgs 
                                                   ring_put_device_elem(a, r, c + 2), ring_put_device_elem(a, r, c + 3));
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) *a.d_size = a.new_size;
+}
+
+// Particle adds from device arrays (rb_add_particles_device): the record
+// [feat | particles | action | next_feat | next_particles | r | not_done | pad] is assembled in the ring
+// from seven arrays.  Almost all of it is the two [N*D] particle blocks, whose record offset (o_p = F)
+// and source rows (N*D floats) are in general not 16-byte aligned.  One workgroup per tile of
+// kPutTile record columns: the work is split by SEGMENT (a table in the launch arguments, walked
+// uniformly by the whole workgroup), so inside a segment consecutive lanes read consecutive source
+// floats (dword loads, any alignment, every source float exactly once) into the tile's LDS image at
+// their record column; the image then leaves as float4 stores aligned on the ring (rec and kPutTile
+// are multiples of 4).  No per-float search for the segment a column belongs to.
+constexpr int kPutTile = 1024;              // record columns per workgroup pass (4 per thread)
+constexpr int kPutSegs = 7;
+struct RingPutSeg {
+  const float* src;                         // [n][len]
+  int off, len;                             // record columns [off, off + len)
+};
+struct RingPutPartArgs {
+  float4* data;
+  int64_t* d_size;
+  RingPutSeg seg[kPutSegs];                 // ascending and adjacent: seg[k + 1].off = seg[k].off + seg[k].len
+  int64_t cap, ptr, n, skip, new_size;
+  int rec, o_nd, ntile;                     // ntile = ceil(rec / kPutTile)
+};
+__global__ __launch_bounds__(256) void ring_put_particles_kernel(RingPutPartArgs a) {
+  __shared__ float4 img4[kPutTile / 4];
+  float* img = reinterpret_cast<float*>(img4);
+  const int tid = threadIdx.x;
+  const int64_t tiles = a.n * a.ntile;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t row = t / a.ntile;
+    const int c0 = (int)(t - row * a.ntile) * kPutTile, c1 = min(c0 + kPutTile, a.rec);
+    const int64_t r = a.skip + row;
+#pragma unroll 1
+    for (int k = 0; k < kPutSegs; ++k) {
+      const RingPutSeg g = a.seg[k];
+      const int lo = max(g.off, c0), hi = min(g.off + g.len, c1);
+      if (lo >= hi) continue;                                   // uniform: the segment misses this tile
+      const float* src = g.src + r * g.len;                     // the source row of this record
+      const bool nd = g.off == a.o_nd;
+      float v[4];                                               // the tile's loads in flight together
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = lo + tid + 256 * j;
+        v[j] = c < hi ? src[c - g.off] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = lo + tid + 256 * j;
+        if (c < hi) img[c - c0] = nd ? 1.0f - v[j] : v[j];      // my_replay_buffer.py:53
+      }
+    }
+    for (int c = max(a.o_nd + 1, c0) + tid; c < c1; c += 256) img[c - c0] = 0.f;   // record pad
+    __syncthreads();
+    int64_t dst = a.ptr + row;
+    if (dst >= a.cap) dst -= a.cap;
+    const int c = c0 + 4 * tid;
+    if (c < c1) a.data[(dst * a.rec + c) >> 2] = img4[tid];
+    __syncthreads();                                            // the image is reused by the next tile
+  }
+  if (blockIdx.x == 0 && tid == 0) *a.d_size = a.new_size;
 }
 
 // The lazy ordering of Ring::read_stream / write_stream: when `s` differs from the noted stream,
@@ -554,7 +616,7 @@ int rb_add_device(rb_handle* h, const float* state, const float* action, const f
   if (n == 0) return 0;
   TD3_ARG(state && action && next_state && reward && done, "null input");
   Ring* r = reinterpret_cast<Ring*>(h);
-  TD3_ARG(!r->particles, "rb_add_device on a particle ring (particle rings have no device add)");
+  TD3_ARG(!r->particles, "rb_add_device on a particle ring (use rb_add_particles_device)");
   TD3_HIP(hipSetDevice(r->device));
   hipStream_t s = stream ? (hipStream_t)stream : r->stream;
   TD3_RC(ring_begin_write(r, s));
@@ -587,6 +649,52 @@ int rb_add_device(rb_handle* h, const float* state, const float* action, const f
   const int64_t total4 = n * a.rec4;
   const int grid = (int)std::min<int64_t>((total4 + 255) / 256, 1024);
   hipLaunchKernelGGL(ring_put_device_kernel, dim3(grid), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  r->ptr = (r->ptr + n) % r->cap;
+  r->size = new_size;
+  return ring_end_write(r, s);
+}
+
+int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, const float* action,
+                            const float* next_feat, const float* next_part, const float* reward,
+                            const float* done, int64_t n, void* stream) {
+  TD3_ARG(n >= 0, "n must be >= 0");
+  TD3_ARG(h != nullptr, "null handle");
+  if (n == 0) return 0;
+  TD3_ARG(feat && part && action && next_feat && next_part && reward && done, "null input");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(r->particles, "rb_add_particles_device on a featured ring (use rb_add_device)");
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_write(r, s));
+  // ptr / size as push_staged: only the last `cap` rows survive when n > cap
+  RingPutPartArgs a{};
+  if (n > r->cap) {
+    a.skip = n - r->cap;
+    r->ptr = (r->ptr + a.skip) % r->cap;
+    n = r->cap;
+    r->size = r->cap;
+  }
+  const int64_t new_size = std::min<int64_t>(r->size + n, r->cap);
+  const int np = r->N * r->D;
+  a.data = reinterpret_cast<float4*>(r->data);
+  a.d_size = r->d_size;
+  a.seg[0] = RingPutSeg{feat, r->o_s, r->sd};
+  a.seg[1] = RingPutSeg{part, r->o_p, np};
+  a.seg[2] = RingPutSeg{action, r->o_a, r->ad};
+  a.seg[3] = RingPutSeg{next_feat, r->o_s2, r->sd};
+  a.seg[4] = RingPutSeg{next_part, r->o_p2, np};
+  a.seg[5] = RingPutSeg{reward, r->o_r, 1};
+  a.seg[6] = RingPutSeg{done, r->o_nd, 1};                 // stored as 1 - done
+  a.cap = r->cap;
+  a.ptr = r->ptr;
+  a.n = n;
+  a.new_size = new_size;
+  a.rec = r->rec;
+  a.o_nd = r->o_nd;
+  a.ntile = (r->rec + kPutTile - 1) / kPutTile;
+  const int grid = (int)std::min<int64_t>(n * a.ntile, 4096);
+  hipLaunchKernelGGL(ring_put_particles_kernel, dim3(grid), dim3(256), 0, s, a);
   TD3_HIP(hipGetLastError());
   r->ptr = (r->ptr + n) % r->cap;
   r->size = new_size;

@@ -7,6 +7,8 @@
 //   TD3_featured.TD3.eval_q     :117-121  -> td3_eval_q
 //   main.py:249-252 (select_action + OU noise + clip) on device rows -> td3_select_action_device;
 //   eval_q on device rows -> td3_eval_q_device (asynchronous, nothing crosses the host)
+//   TD3_particles.TD3.select_action / eval_q (TD3_particles.py:153-164) on device rows ->
+//   td3_select_action_particles_device / td3_eval_q_particles_device (particles read in place)
 //   TD3_base save/load         TD3_base.py:26-50 -> td3_get_params / td3_set_params
 //
 // HBM layout
@@ -309,6 +311,10 @@ struct ActPlan {       // select_action / eval_q at small batch
   unsigned seq[2] = {0, 0};
   int fail_test = 0;                          // td3_debug_act_fail: queries left whose poll "times out"
   int64_t* d_iota = nullptr;
+  // device-resident particle queries: the caller's [dev_n][N*D] rows the encoder stage reads in place,
+  // set by the query before it runs the stages (launch arguments are copied at launch)
+  const float* dev_part = nullptr;
+  int dev_n = 0;
   EvalB A, Q[2];
   std::vector<void*> tables;
   std::vector<Stage> act, evalq;
@@ -2680,9 +2686,14 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
 
 // select_action / eval_q of TD3_particles (TD3_particles.py:153-164): the particles of the n
 // query states are uploaded packed ([n][N*D], rows 0..n-1), the encoders read them in place.
-static int build_act_particles(td3_handle* h, int Bp, ActPlan** out) {
-  auto it = h->act.find(Bp);
-  if (it != h->act.end()) {
+// dev: a plan of the device-resident queries (td3_handle::act_dev, as build_act's): device scratch at
+// every size, and the encoder stage reads the CALLER's particle rows where they are -- the query sets
+// ActPlan::dev_part / dev_n before it runs the stages (data = part, rec = N*D, identity idx, B = n;
+// enc_fwd_kernel writes zeros for rows >= B without touching data).  Such a plan has no pbatch.
+static int build_act_particles(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
+  auto& plans = dev ? h->act_dev : h->act;
+  auto it = plans.find(Bp);
+  if (it != plans.end()) {
     *out = it->second.get();
     return 0;
   }
@@ -2695,7 +2706,7 @@ static int build_act_particles(td3_handle* h, int Bp, ActPlan** out) {
   const NetL& q1 = h->critic.nets[0];
   const NetL& q2 = h->critic.nets[cdq ? 1 : 0];
   const int lda = an.lin[0].Kp, ldq = q1.lin[0].Kp;
-  const size_t io_floats = (size_t)Bp * (lda + 2 * ldq + (size_t)N * D + 32 + 2 * 32) + 8 * 64;
+  const size_t io_floats = (size_t)Bp * (lda + 2 * ldq + (dev ? 0 : (size_t)N * D) + 32 + 2 * 32) + 8 * 64;
   size_t floats = io_floats + 2 * (size_t)Bp + eval_floats(an, Bp, false, norm) +
                   2 * eval_floats(q1, Bp, false, norm) + 8192;
   TD3_HIP(hipMalloc(&A->scratch, floats * 4));
@@ -2703,11 +2714,11 @@ static int build_act_particles(td3_handle* h, int Bp, ActPlan** out) {
   TD3_HIP(hipDeviceSynchronize());
   Scratch S{A->scratch, floats, 0};
   IoCarve io{&S};
-  TD3_RC(map_io(A.get(), io_floats, &io));
+  if (!dev) TD3_RC(map_io(A.get(), io_floats, &io));
   A->X_S = io.take((size_t)Bp * lda, &A->hX_S);
   A->X_SA = io.take((size_t)Bp * ldq, &A->hX_SA);
   A->XQ2 = io.take((size_t)Bp * ldq, &A->hXQ2);
-  A->pbatch = io.take((size_t)Bp * N * D, &A->hpbatch);
+  if (!dev) A->pbatch = io.take((size_t)Bp * N * D, &A->hpbatch);
   A->out = io.take((size_t)Bp * 32, &A->hout);
   A->ldo = 32;
   for (int j = 0; j < 2; ++j) A->q[j] = io.take((size_t)Bp * 32, &A->hq[j]);
@@ -2732,6 +2743,18 @@ static int build_act_particles(td3_handle* h, int Bp, ActPlan** out) {
     a.N = N;
     a.D = D;
     a.ntile = (N + 31) / 32;
+    if (dev) {
+      const ActPlan* Ap = A.get();                    // owned by the plan map: outlives its stages
+      st.push_back({name,
+                    [=](hipStream_t s) {
+                      EncFwdArgs b = a;
+                      b.data = Ap->dev_part;
+                      b.B = Ap->dev_n;
+                      return launch_enc_fwd(b, s);
+                    },
+                    0, "td3::enc_fwd_kernel"});
+      return;
+    }
     st.push_back({name, [=](hipStream_t s) { return launch_enc_fwd(a, s); }, 0, "td3::enc_fwd_kernel"});
   };
   auto head = [&](const NetL& n, const float* Pp, EvalB& e, int mode) {
@@ -2793,7 +2816,7 @@ static int build_act_particles(td3_handle* h, int Bp, ActPlan** out) {
   }
   (void)ad;
   *out = A.get();
-  h->act[Bp] = std::move(A);
+  plans[Bp] = std::move(A);
   return 0;
 }
 
@@ -3452,21 +3475,10 @@ static int device_query_stream(td3_handle* h, void* stream, hipStream_t* out) {
   return 0;
 }
 
-int td3_select_action_device(td3_handle* h, const float* state, int n, const td3_explore* ex,
-                             float* action_out, void* stream) {
-  TD3_ARG(n > 0, "n must be positive");
-  TD3_ARG(h && state && action_out, "null argument");
-  TD3_ARG(!h->particles, "particle learner: no device-resident query (use td3_select_action_particles)");
-  TD3_HIP(hipSetDevice(h->cfg.device));
-  const int Bp = pad32(n);
-  ActPlan* A;
-  TD3_RC(build_act(h, Bp, &A, true));
-  hipStream_t s;
-  TD3_RC(device_query_stream(h, stream, &s));
-  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, state, h->sd, n, Bp, A->X_S, pad32(h->sd), 0,
-                     (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
-  TD3_HIP(hipGetLastError());
-  TD3_RC(run_stages(A->act, s));
+// The epilogue of both device policy queries: the head's rows (stride A->ldo) -> action_out [n][ad],
+// with the exploration noise of `ex` and the clip to cfg.max_action (ex NULL: the rows as they are).
+static int explore_rows(td3_handle* h, const ActPlan* A, int n, const td3_explore* ex, float* action_out,
+                        hipStream_t s) {
   ExploreArgs e{};
   e.pi = A->out;
   e.ldp = A->ldo;
@@ -3489,10 +3501,28 @@ int td3_select_action_device(td3_handle* h, const float* state, int n, const td3
   return launch_explore(e, s);
 }
 
+int td3_select_action_device(td3_handle* h, const float* state, int n, const td3_explore* ex,
+                             float* action_out, void* stream) {
+  TD3_ARG(n > 0, "n must be positive");
+  TD3_ARG(h && state && action_out, "null argument");
+  TD3_ARG(!h->particles, "particle learner: use td3_select_action_particles_device");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  const int Bp = pad32(n);
+  ActPlan* A;
+  TD3_RC(build_act(h, Bp, &A, true));
+  hipStream_t s;
+  TD3_RC(device_query_stream(h, stream, &s));
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, state, h->sd, n, Bp, A->X_S, pad32(h->sd), 0,
+                     (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
+  TD3_HIP(hipGetLastError());
+  TD3_RC(run_stages(A->act, s));
+  return explore_rows(h, A, n, ex, action_out, s);
+}
+
 int td3_eval_q_device(td3_handle* h, const float* state, const float* action, int n, float* q_out, void* stream) {
   TD3_ARG(n > 0, "n must be positive");
   TD3_ARG(h && state && action && q_out, "null argument");
-  TD3_ARG(!h->particles, "particle learner: no device-resident query (use td3_eval_q_particles)");
+  TD3_ARG(!h->particles, "particle learner: use td3_eval_q_particles_device");
   TD3_HIP(hipSetDevice(h->cfg.device));
   const int Bp = pad32(n), ld = pad32(h->sd + h->ad);
   ActPlan* A;
@@ -3633,6 +3663,65 @@ int td3_eval_q_particles(td3_handle* h, const float* feat, const float* part, co
   for (int j = 0; j < 2; ++j) {
     const int k = cdq ? j : 0;
     TD3_RC(get_rows(q_out + (size_t)j * n * ad, ad, A->q[k], A->hq[k], 32, n, s));
+  }
+  return 0;
+}
+
+// The particle learner's device queries.  The features (and actions) are packed into the MLP input rows
+// behind the kEncC2 pooled columns; the particles are NOT copied: the encoder stage reads the caller's
+// [n][N*D] rows in place (build_act_particles, dev) and writes zeros for the pad rows n..Bp-1.
+int td3_select_action_particles_device(td3_handle* h, const float* feat, const float* part, int n,
+                                       const td3_explore* ex, float* action_out, void* stream) {
+  TD3_ARG(n > 0, "n must be positive");
+  TD3_ARG(h && feat && part && action_out, "null argument");
+  TD3_ARG(h->particles, "featured learner: use td3_select_action_device");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  const int Bp = pad32(n);
+  ActPlan* A;
+  TD3_RC(build_act_particles(h, Bp, &A, true));
+  hipStream_t s;
+  TD3_RC(device_query_stream(h, stream, &s));
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, feat, h->sd, n, Bp, A->X_S, h->actor.nets[0].lin[0].Kp,
+                     kEncC2, (float*)nullptr, 0, 0, (float*)nullptr, 0, 0);
+  TD3_HIP(hipGetLastError());
+  A->dev_part = part;
+  A->dev_n = n;
+  TD3_RC(run_stages(A->act, s));
+  // the head is the tanh policy (TD3_particles.py:68); the clip is main.py:252's, to cfg.max_action
+  return explore_rows(h, A, n, ex, action_out, s);
+}
+
+int td3_eval_q_particles_device(td3_handle* h, const float* feat, const float* part, const float* action, int n,
+                                float* q_out, void* stream) {
+  TD3_ARG(n > 0, "n must be positive");
+  TD3_ARG(h && feat && part && action && q_out, "null argument");
+  TD3_ARG(h->particles, "featured learner: use td3_eval_q_device");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  const int Bp = pad32(n), F = h->sd, ad = h->ad;
+  const int ldq = h->critic.nets[0].lin[0].Kp;
+  const bool cdq = h->cdq != 0;
+  ActPlan* A;
+  TD3_RC(build_act_particles(h, Bp, &A, true));
+  hipStream_t s;
+  TD3_RC(device_query_stream(h, stream, &s));
+  float* X2 = cdq ? A->XQ2 : nullptr;                       // Q2's own input rows (its own encoder)
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, feat, F, n, Bp, A->X_SA, ldq, kEncC2, X2, ldq, kEncC2,
+                     (float*)nullptr, 0, 0);
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, action, ad, n, Bp, A->X_SA, ldq, kEncC2 + F, X2, ldq,
+                     kEncC2 + F, (float*)nullptr, 0, 0);
+  TD3_HIP(hipGetLastError());
+  A->dev_part = part;
+  A->dev_n = n;
+  TD3_RC(run_stages(A->evalq, s));
+  for (int j = 0; j < 2; ++j) {      // the live rows of the stride-32 head outputs -> q_out[j][n][ad]
+    ExploreArgs e{};                 // explore_kernel's plain form: a strided row copy
+    e.pi = A->q[cdq ? j : 0];
+    e.ldp = 32;
+    e.action_out = q_out + (size_t)j * n * ad;
+    e.n = n;
+    e.ad = ad;
+    e.plain = 1;
+    TD3_RC(launch_explore(e, s));
   }
   return 0;
 }

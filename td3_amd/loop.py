@@ -25,7 +25,10 @@ The gym / MuJoCo / SPlisHSPlasH environments are not part of this build (not ins
 ``DeviceTrainLoop`` is the same order for environments that live on the GPU (``SyntheticVecEnv``:
 the stand-in as torch ops on ``[n_envs]`` device rows): ``select_action_device`` applies policy,
 OU noise and clip on the device, ``add_batch`` on CUDA tensors assembles the ring records from
-device memory, and no transition crosses the host (``tools/bench_rollout.py``).
+device memory, and no transition crosses the host (``tools/bench_rollout.py``).  With
+``SyntheticParticleVecEnv`` (states are ``(features, particles)`` tuples) and the particle learner
+and ring it is the same loop: ``rb_add_particles_device`` builds the wide records in the ring and the
+query's encoder reads the simulator's particle tensor in place.
 """
 from __future__ import annotations
 
@@ -35,7 +38,8 @@ import numpy as np
 
 from .exploration import OrnsteinUhlenbeckActionNoise
 
-__all__ = ["add_to_replay_buffer", "TrainLoop", "SyntheticEnv", "Box", "SyntheticVecEnv", "DeviceTrainLoop"]
+__all__ = ["add_to_replay_buffer", "TrainLoop", "SyntheticEnv", "Box", "SyntheticVecEnv",
+           "SyntheticParticleVecEnv", "DeviceTrainLoop"]
 
 
 def add_to_replay_buffer(replay_buffer, state, action, reward, next_state, done_bool, relabels=()):
@@ -203,6 +207,62 @@ class SyntheticVecEnv:
         return nxt, reward, done, done.clone()
 
 
+class SyntheticParticleVecEnv:
+    """The particle-observation stand-in (the water-pouring environment's shapes): ``state`` is the
+    tuple (features ``[n_envs][F]``, particles ``[n_envs][N][D]``) of fp32 device tensors,
+    p' = tanh(p P^T + a V^T) per particle, f' = tanh(f W^T + a U^T + mean_N(p) M^T),
+    r = -|f'|^2 / F, episodes of fixed length.  Auto-reset and the ``step`` return as
+    ``SyntheticVecEnv``, with ``next_state`` a tuple too."""
+
+    def __init__(self, n_envs, feat_dim, n_particles, particle_dim, action_dim, max_action=1.0,
+                 max_episode_steps=1000, seed=0, device=None):
+        import torch
+        rs = np.random.RandomState(seed)
+        F, N, D, A = int(feat_dim), int(n_particles), int(particle_dim), int(action_dim)
+        self.n_envs = int(n_envs)
+        self.observation_space = (Box(-np.inf, np.inf, (F,)), Box(-np.inf, np.inf, (N, D)))
+        self.action_space = Box(-max_action, max_action, (A,))
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+
+        def mat(rows, cols):                   # x [.., rows] @ mat -> [.., cols], unit-variance rows in
+            m = rs.standard_normal((rows, cols)) / np.sqrt(rows)
+            return torch.as_tensor(m, dtype=torch.float32, device=self.device)
+
+        self._Wt, self._Ut, self._Mt = mat(F, F), mat(A, F), mat(D, F)
+        self._Pt, self._Vt = mat(D, D), mat(A, D)
+        self._dims = (F, N, D)
+        self._max_episode_steps = int(max_episode_steps)
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+        self._t = torch.zeros(self.n_envs, dtype=torch.int64, device=self.device)
+        self.state = None
+
+    def _fresh(self):
+        import torch
+        F, N, D = self._dims
+        kw = dict(generator=self._gen, device=self.device, dtype=torch.float32)
+        return 0.1 * torch.randn((self.n_envs, F), **kw), torch.randn((self.n_envs, N, D), **kw)
+
+    def reset(self):
+        self._t.zero_()
+        self.state = self._fresh()
+        return self.state
+
+    def step(self, action):
+        import torch
+        f, p = self.state
+        a = action.to(torch.float32)
+        p2 = torch.tanh(p @ self._Pt + (a @ self._Vt)[:, None, :])
+        f2 = torch.tanh(f @ self._Wt + a @ self._Ut + p.mean(dim=1) @ self._Mt)
+        reward = -(f2 * f2).sum(dim=1) / f2.shape[1]
+        self._t += 1
+        done = self._t >= self._max_episode_steps
+        ff, fp = self._fresh()
+        self.state = (torch.where(done[:, None], ff, f2), torch.where(done[:, None, None], fp, p2))
+        self._t.masked_fill_(done, 0)
+        return (f2, p2), reward, done, done.clone()
+
+
 class DeviceTrainLoop:
     """``main.py:240-289``'s order per tick over all rows of a GPU-resident vector environment
     (``state`` attribute, ``reset()``, ``step(actions) -> (next_state, reward, done, time_limit)``
@@ -211,7 +271,8 @@ class DeviceTrainLoop:
     ``train_steps_per_tick`` gradient steps from tick ``start_training`` on; rows whose episode
     ended have their noise reset at the next query.  Every piece only queues GPU work
     (``select_action_device``, ``rb_add_device``, ``train``): the host reads nothing back and
-    keeps only the tick counter."""
+    keeps only the tick counter.  A state may be one tensor (featured learner and ring) or the
+    tuple ``(features, particles)`` of ``SyntheticParticleVecEnv`` (particle learner and ring)."""
 
     def __init__(self, env, policy, replay_buffer, *, start_policy, start_training, batch_size, expl_noise,
                  done_swap=True, train_steps_per_tick=1, seed=0):
@@ -235,21 +296,24 @@ class DeviceTrainLoop:
         t0 = time.perf_counter()
         for t in range(int(max_ticks)):
             if t < self.start_policy:
-                action = (torch.rand((n, ad), device=state.device, dtype=torch.float32) * 2 - 1) * ma
+                action = (torch.rand((n, ad), device=policy.device, dtype=torch.float32) * 2 - 1) * ma
                 if ended is not None:
                     self.noise.reset(ended)
             else:
                 action = policy.select_action_device(state, noise=self.noise, reset=ended)
             next_state, reward, done, time_limit = env.step(action)
             done_bool = (done & ~time_limit) if self.done_swap else done
-            rb.add_batch(state, action, next_state, reward, done_bool)
+            if isinstance(state, tuple):
+                rb.add_batch(*state, action, *next_state, reward, done_bool)
+            else:
+                rb.add_batch(state, action, next_state, reward, done_bool)
             state, ended = env.state, done
             if t >= self.start_training:
                 for _ in range(self.train_steps_per_tick):
                     policy.train(rb, self.batch_size)
                     grad_steps += 1
         policy.sync()
-        torch.cuda.synchronize(state.device)
+        torch.cuda.synchronize(policy.device)
         dt = time.perf_counter() - t0
         steps = int(max_ticks) * n
         return {"ticks": int(max_ticks), "env_steps": steps, "grad_steps": grad_steps, "seconds": dt,

@@ -484,7 +484,13 @@ class ReplayBuffer_particles(object):
             self.flush()
 
     def add_batch(self, feat, part, action, next_feat, next_part, reward, done):
+        """Bulk add of n transitions.  Torch CUDA tensors (a GPU-resident environment's rows, any
+        float dtype; particles ``[n][N][D]`` or ``[n][N*D]``) go from device memory straight into
+        the ring (``rb_add_particles_device``): no host copy, no synchronisation."""
         self.flush()
+        if _is_cuda_tensor(feat):
+            self._add_batch_device(feat, part, action, next_feat, next_part, reward, done)
+            return
         F, npd, A = self.feat_dim, self._np(), self.action_dim
         f = np.ascontiguousarray(feat, dtype=np.float64).reshape(-1, F)
         n = f.shape[0]
@@ -498,6 +504,28 @@ class ReplayBuffer_particles(object):
             self._shadow.put_batch(arrs[:6] + [1. - arrs[6]], n)
         check(self._lib.rb_add_particles(self._h, *[_lib.dptr(x) for x in arrs], n, self._stream()),
               "rb_add_particles")
+
+    def _add_batch_device(self, feat, part, action, next_feat, next_part, reward, done):
+        torch = _torch()
+        dev = self.device
+
+        def rows(x, cols):
+            x = torch.as_tensor(x, device=dev).to(torch.float32)
+            return x.reshape(-1, cols).contiguous() if cols else x.reshape(-1).contiguous()
+
+        F, npd, A = self.feat_dim, self._np(), self.action_dim
+        ts = [rows(feat, F), rows(part, npd), rows(action, A), rows(next_feat, F), rows(next_part, npd),
+              rows(reward, 0), rows(done, 0)]
+        n = ts[0].shape[0]
+        if any(t.shape[0] != n for t in ts):
+            raise ValueError("add_batch: the seven inputs must have the same number of rows")
+        if self._shadow is not None:
+            self._shadow.valid = False           # rows the host never saw: save() writes the ring
+        # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
+        # the blocks freed with them are reused only after the add read them
+        with self._torch_order():
+            check(self._lib.rb_add_particles_device(self._h, *[t.data_ptr() for t in ts], n, self._stream()),
+                  "rb_add_particles_device")
 
     def flush(self, stream=None):
         _flush_stage(self, stream)
@@ -549,6 +577,12 @@ class ReplayBuffer_particles(object):
             c += w
         return o
 
+    def _records(self):
+        n = self.max_size
+        rec = np.empty((n, self.record_floats), dtype=np.float32)
+        check(self._lib.rb_read_records(self._h, 0, n, _lib.fptr(rec)), "rb_read_records")
+        return rec
+
     def save(self, folder):
         """my_replay_buffer.py:24-32 (ptr / size pickled with protocol 4, arrays np.save'd; the
         float64 host shadow when kept)."""
@@ -560,8 +594,7 @@ class ReplayBuffer_particles(object):
             _save_folder(folder, info.ptr, info.size, sh.arrays)
             return
         n = self.max_size
-        rec = np.empty((n, self.record_floats), dtype=np.float32)
-        check(self._lib.rb_read_records(self._h, 0, n, _lib.fptr(rec)), "rb_read_records")
+        rec = self._records()
         shapes = self._shapes(n)
         _save_folder(folder, info.ptr, info.size,
                      {name: rec[:, c:c + w].astype(np.float64).reshape(shapes[name])
