@@ -24,6 +24,9 @@
  *   td3_eval_q_device    TD3.eval_q on device rows
  *   td3_*_particles      TD3_particles.TD3 (set encoder)  TD3_particles.py:136-224
  *   rb_add_particles_device   ReplayBuffer_particles.add on device rows  my_replay_buffer.py:46-56
+ *   rb_add_device_hindsight / rb_add_particles_device_hindsight
+ *                        add_to_replay_buffer with --hindsight_number K on device rows: each
+ *                        transition and its K relabels in one fan-out add      main.py:70-91
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -120,6 +123,34 @@ int rb_add_particles(rb_handle* h, const double* feat, const double* part, const
 int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, const float* action,
                             const float* next_feat, const float* next_part, const float* reward,
                             const float* done, int64_t n, void* stream);
+/* Hindsight fan-out adds (main.py:70-91 on device rows): each of the n source transitions is stored
+ * 1 + k times.  With E[i*(1+k)] = transition i unchanged and E[i*(1+k) + j] (j = 1..k) = the same
+ * transition with goals[i][j-1][0..g) written into feature columns cols[0..g) of BOTH state and
+ * next_state (feat and next_feat on a particle ring) and rewards[i][j-1] as its reward, the ring
+ * records, ptr and size after the call are bit for bit those of rb_add_device /
+ * rb_add_particles_device given the n*(1+k) rows of E: rows ptr, ptr+1, ... (wrapping), only the last
+ * max_size rows of E when n*(1+k) > max_size (the first surviving row may be a relabel in the
+ * middle of a transition), not_done = 1.0f - done, a zeroed pad.  The source rows are read once per
+ * transition by the particle form (the two particle blocks are not re-read per copy).
+ * Asynchronous on `stream` and ordered exactly as the plain device adds; the device inputs, goals and
+ * rewards included, must stay valid until that stream's work has completed, `hs` itself is host
+ * memory read during the call only.  Checked in this order, each failure returning -1 with a message
+ * naming the field: n >= 0; hs (non-null, k, g, goals, rewards, cols non-negative and distinct);
+ * the handle; the ring kind (as rb_add_device / rb_add_particles_device); cols below state_dim
+ * (particle rings: feat_dim).  n == 0 then returns 0. */
+typedef struct rb_hindsight {
+  int k;                 /* relabels per transition, 1..64 */
+  int g;                 /* goal columns, 1..8 */
+  int cols[8];           /* distinct feature columns in [0, state_dim) (particle rings: [0, feat_dim)) */
+  const float* goals;    /* device [n][k][g] */
+  const float* rewards;  /* device [n][k] */
+} rb_hindsight;
+int rb_add_device_hindsight(rb_handle* h, const float* state, const float* action, const float* next_state,
+                            const float* reward, const float* done, int64_t n, const rb_hindsight* hs,
+                            void* stream);
+int rb_add_particles_device_hindsight(rb_handle* h, const float* feat, const float* part, const float* action,
+                                      const float* next_feat, const float* next_part, const float* reward,
+                                      const float* done, int64_t n, const rb_hindsight* hs, void* stream);
 /* The 7 tensors of ReplayBuffer_particles.sample (:58-69) into device outputs. */
 int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float* action, float* next_feat,
                         float* next_part, float* reward, float* not_done, const int64_t* inject_idx,

@@ -45,6 +45,11 @@ class td3_explore(C.Structure):
                 ("inject_z", C.c_void_p), ("z_out", C.c_void_p)]
 
 
+class rb_hindsight(C.Structure):
+    _fields_ = [("k", C.c_int), ("g", C.c_int), ("cols", C.c_int * 8), ("goals", C.c_void_p),
+                ("rewards", C.c_void_p)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -60,6 +65,9 @@ SIGNATURES = {
     "rb_add_records": (C.c_int, [_P, _F, C.c_int64, _P]),
     "rb_add_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rb_add_particles_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rb_add_device_hindsight": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(rb_hindsight), _P]),
+    "rb_add_particles_device_hindsight": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                                    C.POINTER(rb_hindsight), _P]),
     "rb_fill_synthetic": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     "rb_sample": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),

@@ -9,6 +9,8 @@
 //   ReplayBuffer_particles          :6-69    -> rb_create_particles / rb_add_particles /
 //                                               rb_sample_particles (same ring, wider record),
 //                                               rb_add_particles_device (device rows)
+//   main.py add_to_replay_buffer    :70-91   -> rb_add_device_hindsight / rb_add_particles_device_hindsight
+//                                               (device rows, each stored with its K relabels)
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -225,6 +227,30 @@ struct RingPutPartArgs {
   int64_t cap, ptr, n, skip, new_size;
   int rec, o_nd, ntile;                     // ntile = ceil(rec / kPutTile)
 };
+// Record columns [c0, c1) of source row r into the tile's LDS image (the caller's barrier follows).
+__device__ __forceinline__ void ring_put_build_tile(const RingPutPartArgs& a, float* img, int64_t r, int c0, int c1,
+                                                    int tid) {
+#pragma unroll 1
+  for (int k = 0; k < kPutSegs; ++k) {
+    const RingPutSeg g = a.seg[k];
+    const int lo = max(g.off, c0), hi = min(g.off + g.len, c1);
+    if (lo >= hi) continue;                                   // uniform: the segment misses this tile
+    const float* src = g.src + r * g.len;                     // the source row of this record
+    const bool nd = g.off == a.o_nd;
+    float v[4];                                               // the tile's loads in flight together
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = lo + tid + 256 * j;
+      v[j] = c < hi ? src[c - g.off] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = lo + tid + 256 * j;
+      if (c < hi) img[c - c0] = nd ? 1.0f - v[j] : v[j];      // my_replay_buffer.py:53
+    }
+  }
+  for (int c = max(a.o_nd + 1, c0) + tid; c < c1; c += 256) img[c - c0] = 0.f;   // record pad
+}
 __global__ __launch_bounds__(256) void ring_put_particles_kernel(RingPutPartArgs a) {
   __shared__ float4 img4[kPutTile / 4];
   float* img = reinterpret_cast<float*>(img4);
@@ -233,27 +259,7 @@ __global__ __launch_bounds__(256) void ring_put_particles_kernel(RingPutPartArgs
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int64_t row = t / a.ntile;
     const int c0 = (int)(t - row * a.ntile) * kPutTile, c1 = min(c0 + kPutTile, a.rec);
-    const int64_t r = a.skip + row;
-#pragma unroll 1
-    for (int k = 0; k < kPutSegs; ++k) {
-      const RingPutSeg g = a.seg[k];
-      const int lo = max(g.off, c0), hi = min(g.off + g.len, c1);
-      if (lo >= hi) continue;                                   // uniform: the segment misses this tile
-      const float* src = g.src + r * g.len;                     // the source row of this record
-      const bool nd = g.off == a.o_nd;
-      float v[4];                                               // the tile's loads in flight together
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = lo + tid + 256 * j;
-        v[j] = c < hi ? src[c - g.off] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = lo + tid + 256 * j;
-        if (c < hi) img[c - c0] = nd ? 1.0f - v[j] : v[j];      // my_replay_buffer.py:53
-      }
-    }
-    for (int c = max(a.o_nd + 1, c0) + tid; c < c1; c += 256) img[c - c0] = 0.f;   // record pad
+    ring_put_build_tile(a, img, a.skip + row, c0, c1, tid);
     __syncthreads();
     int64_t dst = a.ptr + row;
     if (dst >= a.cap) dst -= a.cap;
@@ -262,6 +268,109 @@ __global__ __launch_bounds__(256) void ring_put_particles_kernel(RingPutPartArgs
     __syncthreads();                                            // the image is reused by the next tile
   }
   if (blockIdx.x == 0 && tid == 0) *a.d_size = a.new_size;
+}
+
+// Hindsight fan-out adds (rb_add_device_hindsight / rb_add_particles_device_hindsight, main.py:70-91):
+// source transition i is stored 1 + K times, as the expanded rows e = i * (1 + K) + j; copy j = 0 is
+// the transition itself, copy j >= 1 has the G goal values goals[i][j - 1][.] in feature columns
+// cols[.] of BOTH states and rewards[i][j - 1] as its reward.  Expanded row skip + row goes to ring
+// row ptr + row (wrapping once), exactly as if the expanded rows had been given to the plain add.
+constexpr int kMaxGoals = 8, kMaxRelabels = 64;
+struct RingHindsight {
+  const float *goals, *rewards;             // [n][k][g], [n][k]
+  int k, g;
+  int cols[kMaxGoals];
+};
+// The relabelled value of state column `sc` (an offset inside the state block) of copy j >= 1.
+__device__ __forceinline__ float hindsight_goal(const RingHindsight& h, int64_t i, int j, int sc, float v) {
+#pragma unroll
+  for (int q = 0; q < kMaxGoals; ++q)
+    if (q < h.g && h.cols[q] == sc) v = h.goals[((i * h.k) + (j - 1)) * h.g + q];
+  return v;
+}
+
+struct RingPutDeviceHsArgs {
+  RingPutDeviceArgs p;                      // p.n / p.skip count EXPANDED rows
+  RingHindsight h;
+};
+__device__ __forceinline__ float ring_put_device_hs_elem(const RingPutDeviceHsArgs& a, int64_t i, int j, int c) {
+  const RingPutDeviceArgs& p = a.p;
+  if (j == 0 || c >= p.o_nd || (c >= p.sd && c < p.o_s2)) return ring_put_device_elem(p, i, c);
+  if (c == p.o_r) return a.h.rewards[i * a.h.k + (j - 1)];
+  if (c < p.sd) return hindsight_goal(a.h, i, j, c, p.state[i * p.sd + c]);
+  return hindsight_goal(a.h, i, j, c - p.o_s2, p.next_state[i * p.sd + (c - p.o_s2)]);
+}
+__global__ __launch_bounds__(256) void ring_put_device_hs_kernel(RingPutDeviceHsArgs a) {
+  const RingPutDeviceArgs& p = a.p;
+  const int64_t total = p.n * p.rec4;
+  const int copies = a.h.k + 1;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = t / p.rec4;
+    const int c = (int)(t - row * p.rec4) * 4;
+    const int64_t e = p.skip + row, i = e / copies;
+    const int j = (int)(e - i * copies);
+    int64_t dst = p.ptr + row;
+    if (dst >= p.cap) dst -= p.cap;
+    p.data[dst * p.rec4 + (c >> 2)] = make_float4(ring_put_device_hs_elem(a, i, j, c), ring_put_device_hs_elem(a, i, j, c + 1),
+                                                  ring_put_device_hs_elem(a, i, j, c + 2), ring_put_device_hs_elem(a, i, j, c + 3));
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *p.d_size = p.new_size;
+}
+
+// The particle form: one workgroup per (source transition, tile), the tile's image built in LDS from
+// the source exactly as ring_put_particles_kernel does -- every source float is read once per
+// transition, not once per copy.  Each thread then takes the float4 of the image it stores into
+// registers and writes it 1 + K times; for a relabel copy it first replaces, in a register copy, the
+// goal columns of feat / next_feat and the reward column that fall inside its own float4.  The LDS
+// image is never patched (copy 0 and every later copy start from the original values), so nothing is
+// ordered between patching and storing, and a tile of particle columns alone stores one register
+// value to 1 + K rows.  p.n / p.skip count EXPANDED rows; p.ptr is the ring row of expanded row skip.
+struct RingPutPartHsArgs {
+  RingPutPartArgs p;
+  RingHindsight h;
+  int o_s, o_s2, o_r, sd;                   // feat at [o_s, o_s + sd), next_feat at [o_s2, ..), reward
+};
+__global__ __launch_bounds__(256) void ring_put_particles_hs_kernel(RingPutPartHsArgs a) {
+  __shared__ float4 img4[kPutTile / 4];
+  float* img = reinterpret_cast<float*>(img4);
+  const RingPutPartArgs& p = a.p;
+  const int tid = threadIdx.x;
+  const int copies = a.h.k + 1;
+  const int64_t i0 = p.skip / copies;                             // first source transition with a surviving copy
+  const int64_t e_end = p.skip + p.n;                             // = (source rows) * copies
+  const int64_t tiles = (e_end / copies - i0) * p.ntile;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t srow = t / p.ntile;
+    const int c0 = (int)(t - srow * p.ntile) * kPutTile, c1 = min(c0 + kPutTile, p.rec);
+    const int64_t i = i0 + srow;
+    ring_put_build_tile(p, img, i, c0, c1, tid);
+    __syncthreads();
+    const int c = c0 + 4 * tid;
+    if (c < c1) {
+      const float4 orig = img4[tid];
+      // does this thread's float4 [c, c + 4) meet feat, next_feat or the reward?
+      const bool in_f = c < a.o_s + a.sd && c + 4 > a.o_s, in_f2 = c < a.o_s2 + a.sd && c + 4 > a.o_s2;
+      const bool in_r = a.o_r >= c && a.o_r < c + 4;
+      const int64_t e0 = i * copies;
+      for (int j = (int)max((int64_t)0, p.skip - e0); j < copies; ++j) {
+        float w[4] = {orig.x, orig.y, orig.z, orig.w};
+        if (j > 0 && (in_f || in_f2 || in_r)) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int cc = c + q;
+            if (cc >= a.o_s && cc < a.o_s + a.sd) w[q] = hindsight_goal(a.h, i, j, cc - a.o_s, w[q]);
+            else if (cc >= a.o_s2 && cc < a.o_s2 + a.sd) w[q] = hindsight_goal(a.h, i, j, cc - a.o_s2, w[q]);
+            else if (cc == a.o_r) w[q] = a.h.rewards[i * a.h.k + (j - 1)];
+          }
+        }
+        int64_t dst = p.ptr + (e0 + j - p.skip);
+        if (dst >= p.cap) dst -= p.cap;
+        p.data[(dst * p.rec + c) >> 2] = make_float4(w[0], w[1], w[2], w[3]);
+      }
+    }
+    __syncthreads();                                            // the image is reused by the next tile
+  }
+  if (blockIdx.x == 0 && tid == 0) *p.d_size = p.new_size;
 }
 
 // The lazy ordering of Ring::read_stream / write_stream: when `s` differs from the noted stream,
@@ -609,6 +718,81 @@ int rb_add_records(rb_handle* h, const float* records, int64_t n, void* stream) 
   return push_staged(r, stage, n, s);
 }
 
+// ptr / size of an add of `rows` rows, as push_staged: only the last `cap` rows survive.  Returns the
+// rows to write and leaves r->ptr at the ring row of the first of them (ring_wrote moves it past
+// them); the first `skip` rows are dropped.
+static int64_t ring_reserve(Ring* r, int64_t rows, int64_t& skip, int64_t& new_size) {
+  skip = 0;
+  if (rows > r->cap) {
+    skip = rows - r->cap;
+    r->ptr = (r->ptr + skip) % r->cap;
+    rows = r->cap;
+    r->size = r->cap;
+  }
+  new_size = std::min<int64_t>(r->size + rows, r->cap);
+  return rows;
+}
+
+// The launch arguments of a device add that stores `rows` ring rows (for a hindsight add: expanded rows).
+static RingPutDeviceArgs ring_put_device_args(Ring* r, const float* state, const float* action,
+                                              const float* next_state, const float* reward, const float* done,
+                                              int64_t rows) {
+  RingPutDeviceArgs a{};
+  rows = ring_reserve(r, rows, a.skip, a.new_size);
+  a.data = reinterpret_cast<float4*>(r->data);
+  a.d_size = r->d_size;
+  a.state = state;
+  a.action = action;
+  a.next_state = next_state;
+  a.reward = reward;
+  a.done = done;
+  a.cap = r->cap;
+  a.ptr = r->ptr;
+  a.n = rows;
+  a.sd = r->sd;
+  a.ad = r->ad;
+  a.o_s2 = r->o_s2;
+  a.o_r = r->o_r;
+  a.o_nd = r->o_nd;
+  a.rec4 = r->rec / 4;
+  return a;
+}
+
+static int ring_put_device_grid(const RingPutDeviceArgs& a) {
+  return (int)std::min<int64_t>((a.n * a.rec4 + 255) / 256, 1024);
+}
+
+static RingPutPartArgs ring_put_part_args(Ring* r, const float* feat, const float* part, const float* action,
+                                          const float* next_feat, const float* next_part, const float* reward,
+                                          const float* done, int64_t rows) {
+  RingPutPartArgs a{};
+  rows = ring_reserve(r, rows, a.skip, a.new_size);
+  const int np = r->N * r->D;
+  a.data = reinterpret_cast<float4*>(r->data);
+  a.d_size = r->d_size;
+  a.seg[0] = RingPutSeg{feat, r->o_s, r->sd};
+  a.seg[1] = RingPutSeg{part, r->o_p, np};
+  a.seg[2] = RingPutSeg{action, r->o_a, r->ad};
+  a.seg[3] = RingPutSeg{next_feat, r->o_s2, r->sd};
+  a.seg[4] = RingPutSeg{next_part, r->o_p2, np};
+  a.seg[5] = RingPutSeg{reward, r->o_r, 1};
+  a.seg[6] = RingPutSeg{done, r->o_nd, 1};                 // stored as 1 - done
+  a.cap = r->cap;
+  a.ptr = r->ptr;
+  a.n = rows;
+  a.rec = r->rec;
+  a.o_nd = r->o_nd;
+  a.ntile = (r->rec + kPutTile - 1) / kPutTile;
+  return a;
+}
+
+// After the launch that wrote `rows` rows at r->ptr.
+static int ring_wrote(Ring* r, int64_t rows, int64_t new_size, hipStream_t s) {
+  r->ptr = (r->ptr + rows) % r->cap;
+  r->size = new_size;
+  return ring_end_write(r, s);
+}
+
 int rb_add_device(rb_handle* h, const float* state, const float* action, const float* next_state,
                   const float* reward, const float* done, int64_t n, void* stream) {
   TD3_ARG(n >= 0, "n must be >= 0");
@@ -620,39 +804,10 @@ int rb_add_device(rb_handle* h, const float* state, const float* action, const f
   TD3_HIP(hipSetDevice(r->device));
   hipStream_t s = stream ? (hipStream_t)stream : r->stream;
   TD3_RC(ring_begin_write(r, s));
-  // ptr / size as push_staged: only the last `cap` rows survive when n > cap
-  RingPutDeviceArgs a{};
-  if (n > r->cap) {
-    a.skip = n - r->cap;
-    r->ptr = (r->ptr + a.skip) % r->cap;
-    n = r->cap;
-    r->size = r->cap;
-  }
-  const int64_t new_size = std::min<int64_t>(r->size + n, r->cap);
-  a.data = reinterpret_cast<float4*>(r->data);
-  a.d_size = r->d_size;
-  a.state = state;
-  a.action = action;
-  a.next_state = next_state;
-  a.reward = reward;
-  a.done = done;
-  a.cap = r->cap;
-  a.ptr = r->ptr;
-  a.n = n;
-  a.new_size = new_size;
-  a.sd = r->sd;
-  a.ad = r->ad;
-  a.o_s2 = r->o_s2;
-  a.o_r = r->o_r;
-  a.o_nd = r->o_nd;
-  a.rec4 = r->rec / 4;
-  const int64_t total4 = n * a.rec4;
-  const int grid = (int)std::min<int64_t>((total4 + 255) / 256, 1024);
-  hipLaunchKernelGGL(ring_put_device_kernel, dim3(grid), dim3(256), 0, s, a);
+  const RingPutDeviceArgs a = ring_put_device_args(r, state, action, next_state, reward, done, n);
+  hipLaunchKernelGGL(ring_put_device_kernel, dim3(ring_put_device_grid(a)), dim3(256), 0, s, a);
   TD3_HIP(hipGetLastError());
-  r->ptr = (r->ptr + n) % r->cap;
-  r->size = new_size;
-  return ring_end_write(r, s);
+  return ring_wrote(r, a.n, a.new_size, s);
 }
 
 int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, const float* action,
@@ -667,38 +822,81 @@ int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, 
   TD3_HIP(hipSetDevice(r->device));
   hipStream_t s = stream ? (hipStream_t)stream : r->stream;
   TD3_RC(ring_begin_write(r, s));
-  // ptr / size as push_staged: only the last `cap` rows survive when n > cap
-  RingPutPartArgs a{};
-  if (n > r->cap) {
-    a.skip = n - r->cap;
-    r->ptr = (r->ptr + a.skip) % r->cap;
-    n = r->cap;
-    r->size = r->cap;
-  }
-  const int64_t new_size = std::min<int64_t>(r->size + n, r->cap);
-  const int np = r->N * r->D;
-  a.data = reinterpret_cast<float4*>(r->data);
-  a.d_size = r->d_size;
-  a.seg[0] = RingPutSeg{feat, r->o_s, r->sd};
-  a.seg[1] = RingPutSeg{part, r->o_p, np};
-  a.seg[2] = RingPutSeg{action, r->o_a, r->ad};
-  a.seg[3] = RingPutSeg{next_feat, r->o_s2, r->sd};
-  a.seg[4] = RingPutSeg{next_part, r->o_p2, np};
-  a.seg[5] = RingPutSeg{reward, r->o_r, 1};
-  a.seg[6] = RingPutSeg{done, r->o_nd, 1};                 // stored as 1 - done
-  a.cap = r->cap;
-  a.ptr = r->ptr;
-  a.n = n;
-  a.new_size = new_size;
-  a.rec = r->rec;
-  a.o_nd = r->o_nd;
-  a.ntile = (r->rec + kPutTile - 1) / kPutTile;
-  const int grid = (int)std::min<int64_t>(n * a.ntile, 4096);
+  const RingPutPartArgs a = ring_put_part_args(r, feat, part, action, next_feat, next_part, reward, done, n);
+  const int grid = (int)std::min<int64_t>(a.n * a.ntile, 4096);
   hipLaunchKernelGGL(ring_put_particles_kernel, dim3(grid), dim3(256), 0, s, a);
   TD3_HIP(hipGetLastError());
-  r->ptr = (r->ptr + n) % r->cap;
-  r->size = new_size;
-  return ring_end_write(r, s);
+  return ring_wrote(r, a.n, a.new_size, s);
+}
+
+// The checks of an rb_hindsight that need no ring (made before the handle is looked at).
+static int hindsight_check(const rb_hindsight* hs) {
+  TD3_ARG(hs != nullptr, "null hs");
+  TD3_ARG(hs->k >= 1 && hs->k <= kMaxRelabels, "hs->k must be in 1..64");
+  TD3_ARG(hs->g >= 1 && hs->g <= kMaxGoals, "hs->g must be in 1..8");
+  TD3_ARG(hs->goals != nullptr, "null hs->goals");
+  TD3_ARG(hs->rewards != nullptr, "null hs->rewards");
+  for (int a = 0; a < hs->g; ++a) {
+    TD3_ARG(hs->cols[a] >= 0, "hs->cols must be non-negative");
+    for (int b = 0; b < a; ++b) TD3_ARG(hs->cols[a] != hs->cols[b], "hs->cols must be distinct");
+  }
+  return 0;
+}
+
+static RingHindsight hindsight_args(const rb_hindsight* hs) {
+  RingHindsight h{};
+  h.goals = hs->goals;
+  h.rewards = hs->rewards;
+  h.k = hs->k;
+  h.g = hs->g;
+  for (int a = 0; a < hs->g; ++a) h.cols[a] = hs->cols[a];
+  return h;
+}
+
+int rb_add_device_hindsight(rb_handle* h, const float* state, const float* action, const float* next_state,
+                            const float* reward, const float* done, int64_t n, const rb_hindsight* hs,
+                            void* stream) {
+  TD3_ARG(n >= 0, "n must be >= 0");
+  TD3_RC(hindsight_check(hs));
+  TD3_ARG(h != nullptr, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(!r->particles, "rb_add_device_hindsight on a particle ring (use rb_add_particles_device_hindsight)");
+  for (int a = 0; a < hs->g; ++a) TD3_ARG(hs->cols[a] < r->sd, "hs->cols must be below state_dim");
+  if (n == 0) return 0;
+  TD3_ARG(state && action && next_state && reward && done, "null input");
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_write(r, s));
+  const RingPutDeviceHsArgs a{ring_put_device_args(r, state, action, next_state, reward, done, n * (1 + hs->k)),
+                              hindsight_args(hs)};
+  hipLaunchKernelGGL(ring_put_device_hs_kernel, dim3(ring_put_device_grid(a.p)), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  return ring_wrote(r, a.p.n, a.p.new_size, s);
+}
+
+int rb_add_particles_device_hindsight(rb_handle* h, const float* feat, const float* part, const float* action,
+                                      const float* next_feat, const float* next_part, const float* reward,
+                                      const float* done, int64_t n, const rb_hindsight* hs, void* stream) {
+  TD3_ARG(n >= 0, "n must be >= 0");
+  TD3_RC(hindsight_check(hs));
+  TD3_ARG(h != nullptr, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(r->particles, "rb_add_particles_device_hindsight on a featured ring (use rb_add_device_hindsight)");
+  for (int a = 0; a < hs->g; ++a) TD3_ARG(hs->cols[a] < r->sd, "hs->cols must be below feat_dim");
+  if (n == 0) return 0;
+  TD3_ARG(feat && part && action && next_feat && next_part && reward && done, "null input");
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_write(r, s));
+  const int copies = 1 + hs->k;
+  const RingPutPartHsArgs a{
+      ring_put_part_args(r, feat, part, action, next_feat, next_part, reward, done, n * copies),
+      hindsight_args(hs), r->o_s, r->o_s2, r->o_r, r->sd};
+  const int64_t src_rows = n - a.p.skip / copies;          // source transitions with a surviving copy
+  const int grid = (int)std::min<int64_t>(src_rows * a.p.ntile, 4096);
+  hipLaunchKernelGGL(ring_put_particles_hs_kernel, dim3(grid), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  return ring_wrote(r, a.p.n, a.p.new_size, s);
 }
 
 int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, void* stream) {

@@ -28,7 +28,9 @@ OU noise and clip on the device, ``add_batch`` on CUDA tensors assembles the rin
 device memory, and no transition crosses the host (``tools/bench_rollout.py``).  With
 ``SyntheticParticleVecEnv`` (states are ``(features, particles)`` tuples) and the particle learner
 and ring it is the same loop: ``rb_add_particles_device`` builds the wide records in the ring and the
-query's encoder reads the simulator's particle tensor in place.
+query's encoder reads the simulator's particle tensor in place.  With ``relabel=`` (hindsight,
+``SyntheticGoalVecEnv``) each tick's transitions and their K relabels are stored by one fan-out add
+(``add_batch_hindsight``): the relabelled rows are never built outside the ring.
 """
 from __future__ import annotations
 
@@ -39,7 +41,7 @@ import numpy as np
 from .exploration import OrnsteinUhlenbeckActionNoise
 
 __all__ = ["add_to_replay_buffer", "TrainLoop", "SyntheticEnv", "Box", "SyntheticVecEnv",
-           "SyntheticParticleVecEnv", "DeviceTrainLoop"]
+           "SyntheticParticleVecEnv", "SyntheticGoalVecEnv", "hindsight_relabel", "DeviceTrainLoop"]
 
 
 def add_to_replay_buffer(replay_buffer, state, action, reward, next_state, done_bool, relabels=()):
@@ -263,6 +265,71 @@ class SyntheticParticleVecEnv:
         return (f2, p2), reward, done, done.clone()
 
 
+class SyntheticGoalVecEnv(SyntheticVecEnv):
+    """A goal-conditioned ``SyntheticVecEnv`` (the shape of the reference's own environment, whose
+    observation carries the goal parameters ``manip_state`` overwrites): the leading
+    ``state_dim - goal_dim`` columns are the physical state with ``SyntheticVecEnv``'s dynamics, the
+    last ``goal_dim`` columns are goal weights, drawn per row at reset (uniform in [0, 1)), held
+    through the episode and copied into ``next_state``.  The reward is
+    r = -|p'|^2 / P + sum_g w_g p'_g over the physical next state p' and the goal weights w.
+    ``sample_goals`` and ``imagine_reward`` are the two hooks of a hindsight ``relabel``
+    (``env._imagine_reward`` / ``env.manip_state``, main.py:70-91); ``goal_cols`` are the columns."""
+
+    def __init__(self, n_envs, state_dim, action_dim, goal_dim, max_action=1.0, max_episode_steps=1000, seed=0,
+                 device=None):
+        self.goal_dim = int(goal_dim)
+        self.phys_dim = int(state_dim) - self.goal_dim
+        if not 1 <= self.goal_dim <= self.phys_dim:
+            raise ValueError("goal_dim must be in 1..state_dim / 2 (the reward weighs goal_dim physical columns)")
+        super().__init__(n_envs, self.phys_dim, action_dim, max_action=max_action,
+                         max_episode_steps=max_episode_steps, seed=seed, device=device)
+        self.observation_space = Box(-np.inf, np.inf, (int(state_dim),))
+        self.goal_cols = list(range(self.phys_dim, int(state_dim)))
+
+    def _fresh(self):
+        import torch
+        w = torch.rand((self.n_envs, self.goal_dim), generator=self._gen, device=self.device, dtype=torch.float32)
+        return torch.cat([super()._fresh(), w], dim=1)
+
+    def sample_goals(self, k):
+        """``[n_envs][k][goal_dim]`` fresh goal weights, from the distribution of ``reset``."""
+        import torch
+        return torch.rand((self.n_envs, int(k), self.goal_dim), generator=self._gen, device=self.device,
+                          dtype=torch.float32)
+
+    def imagine_reward(self, next_state, goals):
+        """The reward of reaching ``next_state`` (``[n][state_dim]``; its own goal columns are not
+        read) under ``goals``: ``[n][goal_dim]`` -> ``[n]``, ``[n][k][goal_dim]`` -> ``[n][k]``."""
+        P, G = self.phys_dim, self.goal_dim
+        p = next_state[:, :P]
+        base = -(p * p).sum(dim=1) / P
+        if goals.dim() == 2:
+            return base + (goals * p[:, :G]).sum(dim=1)
+        return base[:, None] + (goals * p[:, None, :G]).sum(dim=2)
+
+    def step(self, action):
+        import torch
+        P = self.phys_dim
+        w = self.state[:, P:]
+        nxt = torch.cat([torch.tanh(self.state[:, :P] @ self._Wt + action.to(torch.float32) @ self._Ut), w], dim=1)
+        reward = self.imagine_reward(nxt, w)
+        self._t += 1
+        done = self._t >= self._max_episode_steps
+        self.state = torch.where(done[:, None], self._fresh(), nxt)
+        self._t.masked_fill_(done, 0)
+        return nxt, reward, done, done.clone()
+
+
+def hindsight_relabel(k):
+    """A ``relabel`` for ``DeviceTrainLoop`` (``--hindsight_number k``, main.py:70-91) over an
+    environment with ``goal_cols``, ``sample_goals`` and ``imagine_reward``: k fresh goals per row
+    and the reward the transition would have earned under each."""
+    def relabel(env, state, action, reward, next_state, done_bool):
+        goals = env.sample_goals(k)
+        return env.goal_cols, goals, env.imagine_reward(next_state, goals)
+    return relabel
+
+
 class DeviceTrainLoop:
     """``main.py:240-289``'s order per tick over all rows of a GPU-resident vector environment
     (``state`` attribute, ``reset()``, ``step(actions) -> (next_state, reward, done, time_limit)``
@@ -272,16 +339,22 @@ class DeviceTrainLoop:
     ended have their noise reset at the next query.  Every piece only queues GPU work
     (``select_action_device``, ``rb_add_device``, ``train``): the host reads nothing back and
     keeps only the tick counter.  A state may be one tensor (featured learner and ring) or the
-    tuple ``(features, particles)`` of ``SyntheticParticleVecEnv`` (particle learner and ring)."""
+    tuple ``(features, particles)`` of ``SyntheticParticleVecEnv`` (particle learner and ring).
+
+    ``relabel(env, state, action, reward, next_state, done_bool)``, when given, returns the tick's
+    hindsight relabels ``(goal_cols, goals [n][K][G], rewards [n][K])`` (main.py:70-91; goals and
+    rewards device tensors, made by the environment's own torch ops); the tick then stores each
+    transition and its K relabels through ``add_batch_hindsight``, still without a host copy."""
 
     def __init__(self, env, policy, replay_buffer, *, start_policy, start_training, batch_size, expl_noise,
-                 done_swap=True, train_steps_per_tick=1, seed=0):
+                 done_swap=True, train_steps_per_tick=1, seed=0, relabel=None):
         from .exploration import DeviceOUNoise
         self.env, self.policy, self.replay_buffer = env, policy, replay_buffer
         self.start_policy, self.start_training = int(start_policy), int(start_training)
         self.batch_size = int(batch_size)
         self.done_swap = done_swap
         self.train_steps_per_tick = int(train_steps_per_tick)
+        self.relabel = relabel
         self.max_action = float(policy.max_action)
         self.noise = DeviceOUNoise(env.n_envs, policy.action_dim, sigma=expl_noise, device=policy.device,
                                    seed=seed)
@@ -303,10 +376,12 @@ class DeviceTrainLoop:
                 action = policy.select_action_device(state, noise=self.noise, reset=ended)
             next_state, reward, done, time_limit = env.step(action)
             done_bool = (done & ~time_limit) if self.done_swap else done
-            if isinstance(state, tuple):
-                rb.add_batch(*state, action, *next_state, reward, done_bool)
+            rows = (*state, action, *next_state) if isinstance(state, tuple) else (state, action, next_state)
+            if self.relabel is None:
+                rb.add_batch(*rows, reward, done_bool)
             else:
-                rb.add_batch(state, action, next_state, reward, done_bool)
+                cols, goals, rewards = self.relabel(env, state, action, reward, next_state, done_bool)
+                rb.add_batch_hindsight(*rows, reward, done_bool, goal_cols=cols, goals=goals, rewards=rewards)
             state, ended = env.state, done
             if t >= self.start_training:
                 for _ in range(self.train_steps_per_tick):

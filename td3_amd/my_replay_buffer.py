@@ -71,6 +71,65 @@ def _flush_stage(buf, stream=None):
         check(buf._lib.rb_add_records(buf._h, buf._stage_ptr, n, stream), "rb_add_records")
 
 
+def _device_rows(dev, arrays, widths, what):
+    """The inputs of a device add as contiguous fp32 tensors on ``dev`` (``[n][w]``, ``[n]`` where
+    the width is 0) and their common row count n; a ValueError naming ``what`` when the counts differ."""
+    torch = _torch()
+    ts = []
+    for x, w in zip(arrays, widths):
+        x = torch.as_tensor(x, device=dev).to(torch.float32)
+        ts.append(x.reshape(-1, w).contiguous() if w else x.reshape(-1).contiguous())
+    n = ts[0].shape[0]
+    if any(t.shape[0] != n for t in ts):
+        raise ValueError(f"{what} must have the same number of rows")
+    return ts, n
+
+
+def _hindsight_device(dev, goal_cols, goals, rewards, n):
+    """The ``rb_hindsight`` of a device add of n transitions and the fp32 tensors it points to."""
+    torch = _torch()
+    g = torch.as_tensor(goals, device=dev).to(torch.float32).contiguous()
+    r = torch.as_tensor(rewards, device=dev).to(torch.float32).contiguous()
+    cols, K, G = _hindsight_dims(goal_cols, g, r, n)
+    hs = _lib.rb_hindsight()
+    hs.k, hs.g = K, G
+    for j, c in enumerate(cols):
+        hs.cols[j] = c
+    hs.goals, hs.rewards = g.data_ptr(), r.data_ptr()
+    return hs, (g, r)
+
+
+def _hindsight_dims(goal_cols, goals, rewards, n):
+    """``(cols, K, G)`` of the relabels of n transitions: ``rewards`` is ``[n][K]``, ``goals``
+    ``[n][K][G]`` (or ``[n][K]`` when there is one goal column); anything else is a ValueError."""
+    cols = [int(c) for c in (goal_cols.tolist() if hasattr(goal_cols, "tolist") else goal_cols)]
+    G = len(cols)
+    if not 1 <= G <= 8:
+        raise ValueError(f"add_batch_hindsight: goal_cols must name 1..8 columns, got {G}")
+    rs, gs = tuple(rewards.shape), tuple(goals.shape)
+    if len(rs) != 2 or rs[0] != n:
+        raise ValueError(f"add_batch_hindsight: rewards must be [n][K] with n = {n}, got {rs}")
+    K = rs[1]
+    if gs != (n, K, G) and not (G == 1 and gs == (n, K)):
+        raise ValueError(f"add_batch_hindsight: goals must be [n][K][G] = {(n, K, G)}, got {gs}")
+    return cols, K, G
+
+
+def _hindsight_expand(arrs, state_slots, reward_slot, cols, K, goals, rewards):
+    """The n * (1 + K) expanded float64 rows of main.py:70-91 from n source rows: row i * (1 + K) is
+    transition i, rows i * (1 + K) + j (j = 1..K) its relabels (goals[i][j - 1] in columns ``cols``
+    of the arrays ``state_slots``, rewards[i][j - 1] in array ``reward_slot``)."""
+    n, width = arrs[state_slots[0]].shape
+    if len(set(cols)) != len(cols) or not all(0 <= c < width for c in cols):
+        raise ValueError(f"add_batch_hindsight: goal_cols must be distinct columns in [0, {width}), got {cols}")
+    out = [np.repeat(a, 1 + K, axis=0) for a in arrs]
+    g = np.asarray(goals, dtype=np.float64).reshape(n, K, len(cols))
+    for k in state_slots:
+        out[k].reshape(n, 1 + K, -1)[:, 1:, cols] = g
+    out[reward_slot].reshape(n, 1 + K)[:, 1:] = np.asarray(rewards, dtype=np.float64).reshape(n, K)
+    return out
+
+
 class _SafeIntUnpickler(pickle.Unpickler):
     """ptr.pkl / size.pkl hold a pickled int (my_replay_buffer.py:93-95); refuse anything else."""
 
@@ -255,27 +314,52 @@ class ReplayBuffer_featured(object):
         check(self._lib.rb_add(self._h, _lib.dptr(s), _lib.dptr(a), _lib.dptr(s2), _lib.dptr(r),
                                _lib.dptr(d), n, self._stream()), "rb_add")
 
-    def _add_batch_device(self, state, action, next_state, reward, done):
-        torch = _torch()
-        dev = self.device
+    def _device_rows(self, arrays, what):
+        sd, ad = self.state_dim, self.action_dim
+        return _device_rows(self.device, arrays, (sd, ad, sd, 0, 0), what)
 
-        def rows(x, cols):
-            x = torch.as_tensor(x, device=dev).to(torch.float32)
-            return x.reshape(-1, cols).contiguous() if cols else x.reshape(-1).contiguous()
-
-        s = rows(state, self.state_dim)
-        n = s.shape[0]
-        a, s2 = rows(action, self.action_dim), rows(next_state, self.state_dim)
-        r, d = rows(reward, 0), rows(done, 0)
-        if not (a.shape[0] == s2.shape[0] == r.shape[0] == d.shape[0] == n):
-            raise ValueError("add_batch: the five inputs must have the same number of rows")
+    def _add_batch_device(self, *arrays):
+        ts, n = self._device_rows(arrays, "add_batch: the five inputs")
         if self._shadow is not None:
             self._shadow.valid = False           # rows the host never saw: save() writes the ring
         # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
         # the blocks freed with them are reused only after the add read them
         with self._torch_order():
-            check(self._lib.rb_add_device(self._h, s.data_ptr(), a.data_ptr(), s2.data_ptr(), r.data_ptr(),
-                                          d.data_ptr(), n, self._stream()), "rb_add_device")
+            check(self._lib.rb_add_device(self._h, *[t.data_ptr() for t in ts], n, self._stream()),
+                  "rb_add_device")
+
+    def add_batch_hindsight(self, state, action, next_state, reward, done, *, goal_cols, goals, rewards):
+        """``add_to_replay_buffer`` with K hindsight relabels per transition (main.py:70-91) for n
+        transitions at once: the ring receives, for each transition in turn, the transition and then
+        its K relabels -- the same row with ``goals[i][j]`` (``[n][K][G]``, or ``[n][K]`` when
+        ``goal_cols`` names one column) in columns ``goal_cols`` of state and next_state and
+        ``rewards[i][j]`` (``[n][K]``) as the reward.  Exactly ``add_batch`` of those n * (1 + K)
+        rows.  CUDA tensors are fanned out by the add kernel itself (``rb_add_device_hindsight``:
+        no expanded copy is made); host arrays are expanded in float64 and take the host add."""
+        self.flush()
+        if _is_cuda_tensor(state):
+            ts, n = self._device_rows((state, action, next_state, reward, done),
+                                       "add_batch_hindsight: the five inputs")
+            hs, keep = _hindsight_device(self.device, goal_cols, goals, rewards, n)
+            if n == 0:
+                return
+            if self._shadow is not None:
+                self._shadow.valid = False       # rows the host never saw: save() writes the ring
+            with self._torch_order():            # as _add_batch_device; `keep` lives until the exit
+                check(self._lib.rb_add_device_hindsight(self._h, *[t.data_ptr() for t in ts], n, hs,
+                                                        self._stream()), "rb_add_device_hindsight")
+            return
+        s = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, self.state_dim)
+        n = s.shape[0]
+        arrs = [s, np.asarray(action, dtype=np.float64).reshape(-1, self.action_dim),
+                np.asarray(next_state, dtype=np.float64).reshape(-1, self.state_dim),
+                np.asarray(reward, dtype=np.float64).reshape(-1), np.asarray(done, dtype=np.float64).reshape(-1)]
+        if any(x.shape[0] != n for x in arrs):
+            raise ValueError("add_batch_hindsight: the five inputs must have the same number of rows")
+        goals, rewards = np.asarray(goals), np.asarray(rewards)
+        cols, K, _ = _hindsight_dims(goal_cols, goals, rewards, n)
+        if n:
+            self.add_batch(*_hindsight_expand(arrs, (0, 2), 3, cols, K, goals, rewards))
 
     def flush(self, stream=None):
         _flush_stage(self, stream)
@@ -505,20 +589,12 @@ class ReplayBuffer_particles(object):
         check(self._lib.rb_add_particles(self._h, *[_lib.dptr(x) for x in arrs], n, self._stream()),
               "rb_add_particles")
 
-    def _add_batch_device(self, feat, part, action, next_feat, next_part, reward, done):
-        torch = _torch()
-        dev = self.device
-
-        def rows(x, cols):
-            x = torch.as_tensor(x, device=dev).to(torch.float32)
-            return x.reshape(-1, cols).contiguous() if cols else x.reshape(-1).contiguous()
-
+    def _device_rows(self, arrays, what):
         F, npd, A = self.feat_dim, self._np(), self.action_dim
-        ts = [rows(feat, F), rows(part, npd), rows(action, A), rows(next_feat, F), rows(next_part, npd),
-              rows(reward, 0), rows(done, 0)]
-        n = ts[0].shape[0]
-        if any(t.shape[0] != n for t in ts):
-            raise ValueError("add_batch: the seven inputs must have the same number of rows")
+        return _device_rows(self.device, arrays, (F, npd, A, F, npd, 0, 0), what)
+
+    def _add_batch_device(self, *arrays):
+        ts, n = self._device_rows(arrays, "add_batch: the seven inputs")
         if self._shadow is not None:
             self._shadow.valid = False           # rows the host never saw: save() writes the ring
         # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
@@ -526,6 +602,39 @@ class ReplayBuffer_particles(object):
         with self._torch_order():
             check(self._lib.rb_add_particles_device(self._h, *[t.data_ptr() for t in ts], n, self._stream()),
                   "rb_add_particles_device")
+
+    def add_batch_hindsight(self, feat, part, action, next_feat, next_part, reward, done, *, goal_cols, goals,
+                            rewards):
+        """``ReplayBuffer_featured.add_batch_hindsight`` for particle transitions: the relabels write
+        ``goals`` into columns ``goal_cols`` of feat and next_feat and ``rewards`` into the reward;
+        the particle blocks, the action and done are the source transition's.  On CUDA tensors
+        ``rb_add_particles_device_hindsight`` reads each source row once and stores it 1 + K times."""
+        self.flush()
+        if _is_cuda_tensor(feat):
+            ts, n = self._device_rows((feat, part, action, next_feat, next_part, reward, done),
+                                       "add_batch_hindsight: the seven inputs")
+            hs, keep = _hindsight_device(self.device, goal_cols, goals, rewards, n)
+            if n == 0:
+                return
+            if self._shadow is not None:
+                self._shadow.valid = False       # rows the host never saw: save() writes the ring
+            with self._torch_order():            # as _add_batch_device; `keep` lives until the exit
+                check(self._lib.rb_add_particles_device_hindsight(self._h, *[t.data_ptr() for t in ts], n, hs,
+                                                                  self._stream()),
+                      "rb_add_particles_device_hindsight")
+            return
+        F, npd, A = self.feat_dim, self._np(), self.action_dim
+        f = np.ascontiguousarray(feat, dtype=np.float64).reshape(-1, F)
+        n = f.shape[0]
+        arrs = [f] + [np.asarray(x, dtype=np.float64).reshape((-1, w) if w else (-1,))
+                      for x, w in ((part, npd), (action, A), (next_feat, F), (next_part, npd), (reward, 0),
+                                   (done, 0))]
+        if any(x.shape[0] != n for x in arrs):
+            raise ValueError("add_batch_hindsight: the seven inputs must have the same number of rows")
+        goals, rewards = np.asarray(goals), np.asarray(rewards)
+        cols, K, _ = _hindsight_dims(goal_cols, goals, rewards, n)
+        if n:
+            self.add_batch(*_hindsight_expand(arrs, (0, 3), 5, cols, K, goals, rewards))
 
     def flush(self, stream=None):
         _flush_stage(self, stream)

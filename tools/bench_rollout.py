@@ -2,7 +2,7 @@
 """Env-steps/s of a rollout on a GPU-resident vector environment: host-vector path vs device path.
 
     python tools/bench_rollout.py [--config featured|particles] [--ticks K] [--warmup W] [--train-steps T]
-                                  [--out FILE]
+                                  [--hindsight K [--n-envs N] [--repeats R]] [--out FILE]
 
 Both paths act on the same ``SyntheticVecEnv`` (HalfCheetah dims: 17 / 6, torch ops on device rows)
 with the same learner and replay ring, act -> env.step -> add per tick over ``n_envs`` rows:
@@ -25,10 +25,24 @@ gives the device add's achieved GB/s at that ``n_envs``: bytes read from the sev
 bytes written to the ring, over the add kernel's device time between two events on the ring's stream
 (median of 20 adds).  ``--add-rows R`` appends one line with that figure alone for an add of R rows
 (a streaming size: whether the kernel or the launch bounds the small adds).
+
+``--hindsight K`` (either config; ``--n-envs``, default 256) measures the device path with K hindsight
+relabels per transition (main.py:70-91) instead, two forms of the store in the same run:
+
+* ``fanout``: ``add_batch_hindsight`` (``rb_add_device_hindsight`` / ``rb_add_particles_device_hindsight``:
+  each source row read once, written 1 + K times with the goal columns and the reward patched);
+* ``expand``: what the API offered before it: the n * (1 + K) rows built with torch
+  (``repeat_interleave`` + index assignments) and handed to ``add_batch``.
+
+One JSON line: for each form the add's effective GB/s (ring bytes written + source bytes read, the same
+numerator for both, over the device time of one call) and the env-steps/s of ``DeviceTrainLoop`` with a
+``relabel`` (median of ``--repeats`` alternated runs), the two ratios, and the fan-out kernel's own time
+between two events on the ring's stream (the method of the plain add's ``device_add_gb_per_s``).
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -142,6 +156,185 @@ def device_rollout(env, pol, rb, ticks, train_steps, batch, sigma=0.1):
     return ticks * n / dt, 1e6 * t_sel / ticks, 1e6 * t_add / ticks
 
 
+HG = 3                                   # goal columns of the hindsight runs (tsp, spill_punish, target_fill)
+
+
+def torch_expand(rows, state_slots, reward_slot, cols_t, goals, rewards):
+    """What a user of the device path had to write before the fan-out add: the n * (1 + K) expanded
+    rows of main.py:70-91 as torch tensors (every array repeated 1 + K times, the goal columns and
+    the rewards of the relabel rows assigned), ready for ``add_batch``."""
+    import torch
+    n, K = rewards.shape
+    out = []
+    for k, x in enumerate(rows):
+        e = x.to(torch.float32).reshape(n, -1).repeat_interleave(1 + K, dim=0)
+        if k in state_slots:
+            e.view(n, 1 + K, -1)[:, 1:, cols_t] = goals
+        elif k == reward_slot:
+            e.view(n, 1 + K)[:, 1:] = rewards
+        out.append(e)
+    return out
+
+
+def use_torch_expansion(rb, particles):
+    """Make ``rb.add_batch_hindsight`` the baseline form: ``torch_expand`` + ``add_batch``."""
+    import torch
+    slots = ((0, 3), 5) if particles else ((0, 2), 3)
+    cols_t = {}
+
+    def add_batch_hindsight(*rows, goal_cols, goals, rewards):
+        key = tuple(goal_cols)
+        if key not in cols_t:
+            cols_t[key] = torch.as_tensor(key, device=rb.device)
+        rb.add_batch(*torch_expand(rows, *slots, cols_t[key], goals, rewards))
+
+    rb.add_batch_hindsight = add_batch_hindsight
+    return rb
+
+
+def particle_relabel(K):
+    """A relabel over ``SyntheticParticleVecEnv`` with the cost profile of the reference's: K draws of
+    HG goal values for the last HG feature columns, rewards recomputed from next_feat (torch ops)."""
+    import torch
+    cols = list(range(PF - HG, PF))
+
+    def relabel(env, state, action, reward, next_state, done_bool):
+        f2 = next_state[0]
+        goals = torch.rand((f2.shape[0], K, HG), device=f2.device, dtype=torch.float32)
+        return cols, goals, -(f2 * f2).sum(dim=1, keepdim=True) / PF + (goals * f2[:, None, :HG]).sum(dim=2)
+
+    return relabel
+
+
+def hindsight_add_gbps(env, rb, relabel, particles, reps=20, warm=3):
+    """Effective GB/s of one hindsight add of env.n_envs transitions through ``rb.add_batch_hindsight``
+    (either form): the bytes the add has to move -- the n * (1 + K) ring records written plus the source
+    arrays, goals and rewards read once -- over the form's device time, median of `reps`.  The time is
+    taken between two events on torch's current stream around the call, twice.  For the GB/s torch's
+    current stream is the ring's own (no hand-off between two streams inside the interval) and a ~1 ms
+    matrix product is queued first, so every launch of the form is queued by the time the first event
+    fires: the interval is the GPU's work alone.  For the latency of one call as the loop makes it, the
+    call runs from torch's default stream on an idle GPU: the interval then also holds the host's time
+    to issue the launches and the two stream hand-offs of ``_TorchOrder``.
+    Returns (GB/s, device us, idle-GPU call us)."""
+    import torch
+    n = env.n_envs
+    busy = torch.randn((4096, 4096), device=env.device)
+    sink = torch.empty_like(busy)
+    state = env.reset()
+    action = torch.zeros((n, env.action_space.shape[0]), device=env.device)
+    next_state, reward, done, _ = env.step(action)
+    cols, goals, rewards = relabel(env, state, action, reward, next_state, done)
+    rows = (*state, action, *next_state) if particles else (state, action, next_state)
+    K = rewards.shape[1]
+    ring_stream = torch.cuda.ExternalStream(int(rb._lib.rb_stream(rb.handle)), device=env.device)
+    ms = {True: [], False: []}
+    for queued in (True, False):
+        for k in range(warm + reps):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(ring_stream) if queued else contextlib.nullcontext():
+                if queued:
+                    torch.mm(busy, busy, out=sink)
+                e0.record()
+                rb.add_batch_hindsight(*rows, reward, done, goal_cols=cols, goals=goals, rewards=rewards)
+                e1.record()
+            torch.cuda.synchronize()
+            if k >= warm:
+                ms[queued].append(e0.elapsed_time(e1))
+    src = sum(x.numel() // n for x in rows) + 2 + K * (len(cols) + 1)
+    nbytes = 4 * n * ((1 + K) * rb.record_floats + src)
+    t = float(np.median(ms[True])) * 1e-3
+    return nbytes / t / 1e9, 1e6 * t, 1e3 * float(np.median(ms[False]))
+
+
+def fanout_kernel_gbps(env, rb, relabel, particles, reps=20):
+    """The fan-out kernel alone, as ``device_add_gbps`` measures the plain add: the same bytes over the
+    device time between two events on the ring's stream around the C call, median of `reps`."""
+    import torch
+    from td3_amd.my_replay_buffer import _hindsight_device
+    n = env.n_envs
+    state = env.reset()
+    action = torch.zeros((n, env.action_space.shape[0]), device=env.device)
+    next_state, reward, done, _ = env.step(action)
+    cols, goals, rewards = relabel(env, state, action, reward, next_state, done)
+    rows = (*state, action, *next_state, reward, done) if particles else (state, action, next_state, reward, done)
+    ts = [t.to(torch.float32).reshape(n, -1).contiguous() for t in rows]
+    K = rewards.shape[1]
+    hs, keep = _hindsight_device(env.device, cols, goals, rewards, n)
+    call = rb._lib.rb_add_particles_device_hindsight if particles else rb._lib.rb_add_device_hindsight
+    stream = torch.cuda.ExternalStream(int(rb._lib.rb_stream(rb.handle)), device=env.device)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        rc = call(rb.handle, *[t.data_ptr() for t in ts], n, hs, None)
+        e1.record(stream)
+        assert rc == 0, rb._lib.td3_last_error()
+        stream.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    nbytes = 4 * n * ((1 + K) * rb.record_floats + sum(t.shape[1] for t in ts) + K * (len(cols) + 1))
+    t = float(np.median(ms)) * 1e-3
+    return nbytes / t / 1e9, 1e6 * t
+
+
+def hindsight_main(args, emit):
+    """``--hindsight K``: the fan-out add against the torch expansion + ``add_batch``, in one run."""
+    import torch
+    from td3_amd.loop import (DeviceTrainLoop, SyntheticGoalVecEnv, SyntheticParticleVecEnv, hindsight_relabel)
+    particles, K, n_envs = args.config == "particles", args.hindsight, args.n_envs
+    if particles:
+        from td3_amd.TD3_particles import TD3
+        from td3_amd.my_replay_buffer import ReplayBuffer_particles as Ring
+        ring_rows, prefill, what = 100_000, 20_000, "SyntheticParticleVecEnv (7 / 350 x 9 / 3)"
+        make_env = lambda: SyntheticParticleVecEnv(n_envs, PF, PN, PD, PA, max_action=MA, max_episode_steps=1000)
+        relabel = particle_relabel(K)
+    else:
+        from td3_amd.TD3_featured import TD3
+        from td3_amd.my_replay_buffer import ReplayBuffer_featured as Ring
+        ring_rows, prefill, what = 1_000_000, 100_000, "SyntheticGoalVecEnv (HalfCheetah dims)"
+        make_env = lambda: SyntheticGoalVecEnv(n_envs, SD, AD, HG, max_action=MA, max_episode_steps=1000)
+        relabel = hindsight_relabel(K)
+    np.random.seed(0)
+    torch.manual_seed(0)
+    env = make_env()
+    pol = TD3(env.observation_space, env.action_space, max_action=MA, norm="layer", device=env.device.index)
+    rings = {}
+    for form in ("fanout", "expand"):
+        rb = Ring(env.observation_space, env.action_space, max_size=ring_rows, device=env.device.index)
+        rb.fill_synthetic(prefill, max_action=MA, seed=1)
+        rings[form] = use_torch_expansion(rb, particles) if form == "expand" else rb
+    add = {form: hindsight_add_gbps(env, rings[form], relabel, particles) for form in rings}
+    kern = fanout_kernel_gbps(env, rings["fanout"], relabel, particles)
+    sps = {form: [] for form in rings}
+    for rep in range(1 + args.repeats):              # the forms alternate; the first pass is the warm-up
+        for form, rb in rings.items():
+            loop = DeviceTrainLoop(env, pol, rb, start_policy=0, start_training=0, batch_size=args.batch,
+                                   expl_noise=0.1, train_steps_per_tick=args.train_steps, relabel=relabel)
+            r = loop.run(args.warmup if rep == 0 else args.ticks)
+            if rep:
+                sps[form].append(r["env_steps_per_s"])
+    fan, exp = float(np.median(sps["fanout"])), float(np.median(sps["expand"]))
+    emit(json.dumps({
+        "metric": f"hindsight K={K} on {what}: act -> env.step -> relabel -> add of each transition and its K "
+                  f"relabels, {args.train_steps} train({args.batch}) per tick; fan-out add vs torch expansion + "
+                  "add_batch",
+        "n_envs": n_envs, "hindsight": K, "goal_cols": HG, "record_floats": int(rings["fanout"].record_floats),
+        "fanout_add_gb_per_s": round(add["fanout"][0], 1), "fanout_add_device_us": round(add["fanout"][1], 2),
+        "fanout_add_idle_call_us": round(add["fanout"][2], 2),
+        "expand_add_gb_per_s": round(add["expand"][0], 1), "expand_add_device_us": round(add["expand"][1], 2),
+        "expand_add_idle_call_us": round(add["expand"][2], 2),
+        "add_fanout_over_expand": round(add["fanout"][0] / add["expand"][0], 3),
+        "fanout_kernel_gb_per_s": round(kern[0], 1), "fanout_kernel_us": round(kern[1], 2),
+        "fanout_steps_per_s": round(fan, 1), "expand_steps_per_s": round(exp, 1),
+        "steps_fanout_over_expand": round(fan / exp, 3),
+        "fanout_steps_per_s_runs": [round(x, 1) for x in sps["fanout"]],
+        "expand_steps_per_s_runs": [round(x, 1) for x in sps["expand"]],
+        "unit": "GB/s (add), env-steps/s (loop)", "higher_is_better": True,
+        "ticks": args.ticks, "warmup": args.warmup, "train_steps_per_tick": args.train_steps, "n_gpus": 1}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=("featured", "particles"), default="featured")
@@ -151,8 +344,21 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--add-rows", type=int, default=0,
                     help="--config particles: one more line, the device add's GB/s for this many rows")
+    ap.add_argument("--hindsight", type=int, default=0,
+                    help="K > 0: compare the fan-out hindsight add with the torch expansion + add_batch instead")
+    ap.add_argument("--n-envs", type=int, default=256, help="--hindsight: environments (default 256)")
+    ap.add_argument("--repeats", type=int, default=3, help="--hindsight: timed loop runs per form (median)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
+    if args.hindsight > 0:
+        def emit_line(line):
+            print(line, flush=True)
+            if args.out:
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+        hindsight_main(args, emit_line)
+        return
     import torch
     from td3_amd.loop import SyntheticParticleVecEnv, SyntheticVecEnv
     particles = args.config == "particles"
