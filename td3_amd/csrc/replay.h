@@ -12,10 +12,21 @@ namespace td3 {
 //   [ features(F) | particles(N*D) | action(A) | next_features(F) | next_particles(N*D) |
 //     reward | not_done | pad ]
 // with sd = F, ad = A; the learner's encoder reads the particle blocks in place (no gather).
+// Either record is an ordered list of fields, Ring::field: the arrays of the kind's rb_add* /
+// rb_sample* calls in argument order, one behind the other from column 0, reward and done (stored
+// as not_done = 1 - done) last.  The host packing, the stand-alone sample and the particle device
+// add walk that table; the o_* names are the same offsets for the code that wants one field.
+struct RingField {
+  int off, len;                    // record columns [off, off + len)
+};
+constexpr int kRingFields = 7;
+
 struct Ring {
   uint64_t gen = 0;                // unique per allocation: captured graphs bake this ring in
   int sd = 0, ad = 0;
   int rec = 0;
+  RingField field[kRingFields] = {};
+  int nfield = 0;                  // 5 (featured) or 7 (particles)
   int o_s = 0, o_a = 0, o_s2 = 0, o_r = 0, o_nd = 0;
   int particles = 0, N = 0, D = 0;  // particle rings only
   int o_p = 0, o_p2 = 0;
@@ -83,5 +94,15 @@ struct GatherArgs {
 };
 
 int launch_gather(const GatherArgs& a, hipStream_t s);
+
+// The ring-side members of a gather from `r` (the caller adds the segments, the batch and the draw).
+inline GatherArgs gather_base(const Ring* r) {
+  GatherArgs a{};
+  a.data = r->data;
+  a.rec = r->rec;
+  a.d_size = r->d_size;
+  a.seed = r->seed;
+  return a;
+}
 
 }  // namespace td3

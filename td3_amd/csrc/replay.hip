@@ -11,6 +11,12 @@
 //                                               rb_add_particles_device (device rows)
 //   main.py add_to_replay_buffer    :70-91   -> rb_add_device_hindsight / rb_add_particles_device_hindsight
 //                                               (device rows, each stored with its K relabels)
+//
+// Both ring kinds are one ring whose record is a table of fields (replay.h Ring::field), filled with
+// the named offsets by ring_layout, the only place that computes an offset.  The host side of the two
+// kinds shares add_host (packing and pushing a host add), sample_fields (stand-alone samples),
+// push_staged (staged records into HBM) and device_add (the launch of a device add); an rb_* entry
+// point of a kind keeps its own argument checks and the kernel it launches.
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -415,6 +421,56 @@ int ring_end_read(Ring* r, hipStream_t s) {
   return 0;
 }
 
+// Writes (records, d_size) on `stream` start after every read and every other-stream write queued
+// so far (Ring::read_stream / write_stream).
+static int ring_begin_write(Ring* r, hipStream_t stream) {
+  TD3_RC(order_after(stream, r->read_stream, r->reads_pending, r->read_ev, r->reads_seen_by));
+  TD3_RC(order_after(stream, r->write_stream, r->writes_pending, r->write_ev, r->writes_seen_by));
+  return 0;
+}
+
+static int ring_end_write(Ring* r, hipStream_t stream) {
+  r->write_stream = stream;
+  r->writes_pending = true;
+  r->writes_seen_by = nullptr;
+  return 0;
+}
+
+// ptr / size of an add of `rows` rows: only the last `cap` rows survive (the ring semantics of
+// my_replay_buffer.py:115-116 applied `rows` times).  Returns the rows to write and leaves r->ptr at
+// the ring row of the first of them (ring_wrote moves it past them); the first `skip` rows are dropped.
+static int64_t ring_reserve(Ring* r, int64_t rows, int64_t& skip, int64_t& new_size) {
+  skip = 0;
+  if (rows > r->cap) {
+    skip = rows - r->cap;
+    r->ptr = (r->ptr + skip) % r->cap;
+    rows = r->cap;
+    r->size = r->cap;
+  }
+  new_size = std::min<int64_t>(r->size + rows, r->cap);
+  return rows;
+}
+
+// After the launches that wrote `rows` rows at r->ptr.
+static int ring_wrote(Ring* r, int64_t rows, int64_t new_size, hipStream_t s) {
+  r->ptr = (r->ptr + rows) % r->cap;
+  r->size = new_size;
+  return ring_end_write(r, s);
+}
+
+// A device add whose launch arguments are built and whose rows are reserved: on the ring's device, on
+// `stream` (or the ring's own) after the reads and writes queued so far; ptr / size then move past the rows.
+template <class Args>
+static int device_add(Ring* r, void (*kernel)(Args), const Args& a, int grid, int64_t rows, int64_t new_size,
+                      void* stream) {
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_write(r, s));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  return ring_wrote(r, rows, new_size, s);
+}
+
 bool ring_alive(const Ring* r, uint64_t gen) {
   std::lock_guard<std::mutex> lk(g_rings_mu);
   return r && g_rings.count(const_cast<Ring*>(r)) && r->gen == gen;
@@ -429,7 +485,28 @@ extern "C" {
 
 static std::atomic<uint64_t> g_ring_gen{0};
 
-static int ring_alloc(Ring* r, int64_t max_size, int device, uint64_t seed, rb_handle** out) {
+// The record of a ring whose dimensions are set: the fields of its kind in C-ABI argument order (a
+// featured ring has no particle blocks), one behind the other, padded to 16 B.
+static void ring_layout(Ring* r) {
+  const int np = r->N * r->D;
+  const struct { int* off; int len; } fields[kRingFields] = {
+      {&r->o_s, r->sd}, {&r->o_p, np}, {&r->o_a, r->ad}, {&r->o_s2, r->sd}, {&r->o_p2, np}, {&r->o_r, 1}, {&r->o_nd, 1}};
+  int c = 0;
+  r->nfield = 0;
+  for (const auto& f : fields) {
+    if (!f.len) continue;
+    *f.off = c;
+    r->field[r->nfield++] = RingField{c, f.len};
+    c += f.len;
+  }
+  r->rec = pad4(c);
+}
+
+// The ring of the dimensions in `dims` (sd, ad and, for a particle ring, particles, N, D).
+static int ring_alloc(const Ring& dims, int64_t max_size, int device, uint64_t seed, rb_handle** out) {
+  TD3_HIP(hipSetDevice(device));
+  Ring* r = new Ring(dims);
+  ring_layout(r);
   r->gen = ++g_ring_gen;
   r->cap = max_size;
   r->seed = seed;
@@ -465,17 +542,10 @@ int rb_create(int state_dim, int action_dim, int64_t max_size, int device, uint6
   TD3_ARG(state_dim > 0 && action_dim > 0, "dims must be positive");
   TD3_ARG(pad4(2 * state_dim + action_dim + 2) <= kMaxRecord, "record too wide");
   TD3_ARG(max_size > 0, "max_size must be positive");
-  TD3_HIP(hipSetDevice(device));
-  Ring* r = new Ring();
-  r->sd = state_dim;
-  r->ad = action_dim;
-  r->o_s = 0;
-  r->o_a = state_dim;
-  r->o_s2 = state_dim + action_dim;
-  r->o_r = 2 * state_dim + action_dim;
-  r->o_nd = r->o_r + 1;
-  r->rec = pad4(2 * state_dim + action_dim + 2);
-  return ring_alloc(r, max_size, device, seed, out);
+  Ring dims;
+  dims.sd = state_dim;
+  dims.ad = action_dim;
+  return ring_alloc(dims, max_size, device, seed, out);
 }
 
 int rb_create_particles(int feat_dim, int n_particles, int particle_dim, int action_dim, int64_t max_size,
@@ -483,23 +553,13 @@ int rb_create_particles(int feat_dim, int n_particles, int particle_dim, int act
   TD3_ARG(out != nullptr, "out is null");
   TD3_ARG(feat_dim > 0 && n_particles > 0 && particle_dim > 0 && action_dim > 0, "dims must be positive");
   TD3_ARG(max_size > 0, "max_size must be positive");
-  TD3_HIP(hipSetDevice(device));
-  Ring* r = new Ring();
-  const int np = n_particles * particle_dim;
-  r->particles = 1;
-  r->N = n_particles;
-  r->D = particle_dim;
-  r->sd = feat_dim;
-  r->ad = action_dim;
-  r->o_s = 0;
-  r->o_p = feat_dim;
-  r->o_a = feat_dim + np;
-  r->o_s2 = r->o_a + action_dim;
-  r->o_p2 = r->o_s2 + feat_dim;
-  r->o_r = r->o_p2 + np;
-  r->o_nd = r->o_r + 1;
-  r->rec = pad4(r->o_nd + 1);
-  return ring_alloc(r, max_size, device, seed, out);
+  Ring dims;
+  dims.particles = 1;
+  dims.N = n_particles;
+  dims.D = particle_dim;
+  dims.sd = feat_dim;
+  dims.ad = action_dim;
+  return ring_alloc(dims, max_size, device, seed, out);
 }
 
 int rb_destroy(rb_handle* h) {
@@ -576,38 +636,14 @@ static int stage_index(const Ring* r, const float* host) {
   return -1;
 }
 
-// Writes (records, d_size) on `stream` start after every read and every other-stream write queued
-// so far (Ring::read_stream / write_stream).
-static int ring_begin_write(Ring* r, hipStream_t stream) {
-  TD3_RC(order_after(stream, r->read_stream, r->reads_pending, r->read_ev, r->reads_seen_by));
-  TD3_RC(order_after(stream, r->write_stream, r->writes_pending, r->write_ev, r->writes_seen_by));
-  return 0;
-}
-
-static int ring_end_write(Ring* r, hipStream_t stream) {
-  r->write_stream = stream;
-  r->writes_pending = true;
-  r->writes_seen_by = nullptr;
-  return 0;
-}
-
 constexpr size_t kPutKernelBytes = 256 << 10;   // adds up to this size take ring_put_kernel
 
-// Copy n packed records (host staging) into the ring at ptr, wrapping (the ring
-// semantics of my_replay_buffer.py:115-116 applied n times).
+// Copy n packed records (host staging) into the ring at ptr, wrapping.
 static int push_staged(Ring* r, const float* host, int64_t n, hipStream_t stream) {
   TD3_RC(ring_begin_write(r, stream));
   const int si = stage_index(r, host);
-  int64_t done = 0;
-  // Only the last `cap` records survive when n > cap.
-  int64_t skip = 0;
-  if (n > r->cap) {
-    skip = n - r->cap;
-    r->ptr = (r->ptr + skip) % r->cap;
-    n = r->cap;
-    r->size = r->cap;
-  }
-  const int64_t new_size = std::min<int64_t>(r->size + n, r->cap);
+  int64_t skip, new_size;
+  n = ring_reserve(r, n, skip, new_size);
   if ((int64_t)n * r->rec <= kPutArgFloats) {       // the records in the kernel arguments
     RingPutArgs pa;
     pa.data = reinterpret_cast<float4*>(r->data);
@@ -620,9 +656,7 @@ static int push_staged(Ring* r, const float* host, int64_t n, hipStream_t stream
     memcpy(pa.rows, host + (size_t)skip * r->rec, (size_t)n * r->rec * sizeof(float));
     hipLaunchKernelGGL(ring_put_args_kernel, dim3(1), dim3(256), 0, stream, pa);
     TD3_HIP(hipGetLastError());
-    r->ptr = (r->ptr + n) % r->cap;
-    r->size = new_size;
-    return ring_end_write(r, stream);
+    return ring_wrote(r, n, new_size, stream);
   }
   if (si >= 0 && (size_t)n * r->rec * sizeof(float) <= kPutKernelBytes) {
     const int64_t total4 = n * (r->rec / 4);
@@ -631,22 +665,41 @@ static int push_staged(Ring* r, const float* host, int64_t n, hipStream_t stream
                        r->cap, r->rec / 4, reinterpret_cast<const float4*>(r->stage_dev[si] + (size_t)skip * r->rec),
                        n, r->ptr, r->d_size, new_size);
     TD3_HIP(hipGetLastError());
-    r->ptr = (r->ptr + n) % r->cap;
   } else {
     const float* src = host + (size_t)skip * r->rec;
-    while (done < n) {
-      int64_t chunk = std::min<int64_t>(n - done, r->cap - r->ptr);
-      TD3_HIP(hipMemcpyAsync(r->data + (size_t)r->ptr * r->rec, src + (size_t)done * r->rec,
+    for (int64_t done = 0, at = r->ptr; done < n; at = 0) {   // up to the end of the ring, then the rest
+      const int64_t chunk = std::min<int64_t>(n - done, r->cap - at);
+      TD3_HIP(hipMemcpyAsync(r->data + (size_t)at * r->rec, src + (size_t)done * r->rec,
                              (size_t)chunk * r->rec * sizeof(float), hipMemcpyHostToDevice, stream));
-      r->ptr = (r->ptr + chunk) % r->cap;
       done += chunk;
     }
     hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, stream, r->d_size, new_size);
     TD3_HIP(hipGetLastError());
   }
-  r->size = new_size;
   if (si >= 0) TD3_HIP(hipEventRecord(r->stage_buf_ev[si], stream));   // the staging buffer is free
-  return ring_end_write(r, stream);
+  return ring_wrote(r, n, new_size, stream);
+}
+
+// A host add of either kind: src[k] is the float64 array [n][field[k].len] of field k, the last one
+// `done`.  The records are packed as fp32 (my_replay_buffer.py:46-56, :109-117) and pushed.
+static int add_host(Ring* r, const double* const src[], int64_t n, void* stream) {
+  TD3_HIP(hipSetDevice(r->device));
+  float small[kPutArgFloats];                      // few records: packed here, shipped as launch arguments
+  const bool few = n * r->rec <= kPutArgFloats;
+  float* stage = few ? small : ensure_stage(r, (size_t)n * r->rec);
+  if (!stage) return -2;
+  const int last = r->nfield - 1;
+  for (int64_t i = 0; i < n; ++i) {
+    float* d = stage + (size_t)i * r->rec;
+    for (int k = 0; k < last; ++k) {
+      const RingField f = r->field[k];
+      const double* x = src[k] + i * f.len;
+      for (int c = 0; c < f.len; ++c) d[f.off + c] = (float)x[c];
+    }
+    d[r->o_nd] = (float)(1.0 - src[last][i]);             // my_replay_buffer.py:114
+    for (int c = r->o_nd + 1; c < r->rec; ++c) d[c] = 0.f;
+  }
+  return push_staged(r, stage, n, stream ? (hipStream_t)stream : r->stream);
 }
 
 int rb_add(rb_handle* h, const double* state, const double* action, const double* next_state,
@@ -657,22 +710,8 @@ int rb_add(rb_handle* h, const double* state, const double* action, const double
   TD3_ARG(state && action && next_state && reward && done, "null input");
   Ring* r = reinterpret_cast<Ring*>(h);
   TD3_ARG(!r->particles, "rb_add on a particle ring (use rb_add_particles)");
-  TD3_HIP(hipSetDevice(r->device));
-  float small[kPutArgFloats];                      // few records: packed here, shipped as launch arguments
-  const bool few = n * r->rec <= kPutArgFloats;
-  float* stage = few ? small : ensure_stage(r, (size_t)n * r->rec);
-  if (!stage) return -2;
-  for (int64_t i = 0; i < n; ++i) {
-    float* d = stage + (size_t)i * r->rec;
-    for (int c = 0; c < r->sd; ++c) d[r->o_s + c] = (float)state[i * r->sd + c];
-    for (int c = 0; c < r->ad; ++c) d[r->o_a + c] = (float)action[i * r->ad + c];
-    for (int c = 0; c < r->sd; ++c) d[r->o_s2 + c] = (float)next_state[i * r->sd + c];
-    d[r->o_r] = (float)reward[i];
-    d[r->o_nd] = (float)(1.0 - done[i]);                  // my_replay_buffer.py:114
-    for (int c = r->o_nd + 1; c < r->rec; ++c) d[c] = 0.f;
-  }
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  return push_staged(r, stage, n, s);
+  const double* const src[] = {state, action, next_state, reward, done};
+  return add_host(r, src, n, stream);
 }
 
 int rb_add_particles(rb_handle* h, const double* feat, const double* part, const double* action,
@@ -684,23 +723,8 @@ int rb_add_particles(rb_handle* h, const double* feat, const double* part, const
   TD3_ARG(feat && part && action && next_feat && next_part && reward && done, "null input");
   Ring* r = reinterpret_cast<Ring*>(h);
   TD3_ARG(r->particles, "rb_add_particles on a featured ring");
-  TD3_HIP(hipSetDevice(r->device));
-  float* stage = ensure_stage(r, (size_t)n * r->rec);
-  if (!stage) return -2;
-  const int np = r->N * r->D;
-  for (int64_t i = 0; i < n; ++i) {                        // my_replay_buffer.py:46-56
-    float* d = stage + (size_t)i * r->rec;
-    for (int c = 0; c < r->sd; ++c) d[r->o_s + c] = (float)feat[i * r->sd + c];
-    for (int c = 0; c < np; ++c) d[r->o_p + c] = (float)part[i * np + c];
-    for (int c = 0; c < r->ad; ++c) d[r->o_a + c] = (float)action[i * r->ad + c];
-    for (int c = 0; c < r->sd; ++c) d[r->o_s2 + c] = (float)next_feat[i * r->sd + c];
-    for (int c = 0; c < np; ++c) d[r->o_p2 + c] = (float)next_part[i * np + c];
-    d[r->o_r] = (float)reward[i];
-    d[r->o_nd] = (float)(1.0 - done[i]);
-    for (int c = r->o_nd + 1; c < r->rec; ++c) d[c] = 0.f;
-  }
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  return push_staged(r, stage, n, s);
+  const double* const src[] = {feat, part, action, next_feat, next_part, reward, done};
+  return add_host(r, src, n, stream);
 }
 
 int rb_add_records(rb_handle* h, const float* records, int64_t n, void* stream) {
@@ -716,21 +740,6 @@ int rb_add_records(rb_handle* h, const float* records, int64_t n, void* stream) 
   if (!stage) return -2;
   memcpy(stage, records, (size_t)n * r->rec * sizeof(float));
   return push_staged(r, stage, n, s);
-}
-
-// ptr / size of an add of `rows` rows, as push_staged: only the last `cap` rows survive.  Returns the
-// rows to write and leaves r->ptr at the ring row of the first of them (ring_wrote moves it past
-// them); the first `skip` rows are dropped.
-static int64_t ring_reserve(Ring* r, int64_t rows, int64_t& skip, int64_t& new_size) {
-  skip = 0;
-  if (rows > r->cap) {
-    skip = rows - r->cap;
-    r->ptr = (r->ptr + skip) % r->cap;
-    rows = r->cap;
-    r->size = r->cap;
-  }
-  new_size = std::min<int64_t>(r->size + rows, r->cap);
-  return rows;
 }
 
 // The launch arguments of a device add that stores `rows` ring rows (for a hindsight add: expanded rows).
@@ -762,21 +771,13 @@ static int ring_put_device_grid(const RingPutDeviceArgs& a) {
   return (int)std::min<int64_t>((a.n * a.rec4 + 255) / 256, 1024);
 }
 
-static RingPutPartArgs ring_put_part_args(Ring* r, const float* feat, const float* part, const float* action,
-                                          const float* next_feat, const float* next_part, const float* reward,
-                                          const float* done, int64_t rows) {
+// The same for a particle ring: src[k] is the device array of field k (the last one, done, is stored as 1 - done).
+static RingPutPartArgs ring_put_part_args(Ring* r, const float* const (&src)[kPutSegs], int64_t rows) {
   RingPutPartArgs a{};
   rows = ring_reserve(r, rows, a.skip, a.new_size);
-  const int np = r->N * r->D;
   a.data = reinterpret_cast<float4*>(r->data);
   a.d_size = r->d_size;
-  a.seg[0] = RingPutSeg{feat, r->o_s, r->sd};
-  a.seg[1] = RingPutSeg{part, r->o_p, np};
-  a.seg[2] = RingPutSeg{action, r->o_a, r->ad};
-  a.seg[3] = RingPutSeg{next_feat, r->o_s2, r->sd};
-  a.seg[4] = RingPutSeg{next_part, r->o_p2, np};
-  a.seg[5] = RingPutSeg{reward, r->o_r, 1};
-  a.seg[6] = RingPutSeg{done, r->o_nd, 1};                 // stored as 1 - done
+  for (int k = 0; k < kPutSegs; ++k) a.seg[k] = RingPutSeg{src[k], r->field[k].off, r->field[k].len};
   a.cap = r->cap;
   a.ptr = r->ptr;
   a.n = rows;
@@ -784,13 +785,6 @@ static RingPutPartArgs ring_put_part_args(Ring* r, const float* feat, const floa
   a.o_nd = r->o_nd;
   a.ntile = (r->rec + kPutTile - 1) / kPutTile;
   return a;
-}
-
-// After the launch that wrote `rows` rows at r->ptr.
-static int ring_wrote(Ring* r, int64_t rows, int64_t new_size, hipStream_t s) {
-  r->ptr = (r->ptr + rows) % r->cap;
-  r->size = new_size;
-  return ring_end_write(r, s);
 }
 
 int rb_add_device(rb_handle* h, const float* state, const float* action, const float* next_state,
@@ -801,13 +795,8 @@ int rb_add_device(rb_handle* h, const float* state, const float* action, const f
   TD3_ARG(state && action && next_state && reward && done, "null input");
   Ring* r = reinterpret_cast<Ring*>(h);
   TD3_ARG(!r->particles, "rb_add_device on a particle ring (use rb_add_particles_device)");
-  TD3_HIP(hipSetDevice(r->device));
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  TD3_RC(ring_begin_write(r, s));
   const RingPutDeviceArgs a = ring_put_device_args(r, state, action, next_state, reward, done, n);
-  hipLaunchKernelGGL(ring_put_device_kernel, dim3(ring_put_device_grid(a)), dim3(256), 0, s, a);
-  TD3_HIP(hipGetLastError());
-  return ring_wrote(r, a.n, a.new_size, s);
+  return device_add(r, ring_put_device_kernel, a, ring_put_device_grid(a), a.n, a.new_size, stream);
 }
 
 int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, const float* action,
@@ -819,14 +808,9 @@ int rb_add_particles_device(rb_handle* h, const float* feat, const float* part, 
   TD3_ARG(feat && part && action && next_feat && next_part && reward && done, "null input");
   Ring* r = reinterpret_cast<Ring*>(h);
   TD3_ARG(r->particles, "rb_add_particles_device on a featured ring (use rb_add_device)");
-  TD3_HIP(hipSetDevice(r->device));
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  TD3_RC(ring_begin_write(r, s));
-  const RingPutPartArgs a = ring_put_part_args(r, feat, part, action, next_feat, next_part, reward, done, n);
+  const RingPutPartArgs a = ring_put_part_args(r, {feat, part, action, next_feat, next_part, reward, done}, n);
   const int grid = (int)std::min<int64_t>(a.n * a.ntile, 4096);
-  hipLaunchKernelGGL(ring_put_particles_kernel, dim3(grid), dim3(256), 0, s, a);
-  TD3_HIP(hipGetLastError());
-  return ring_wrote(r, a.n, a.new_size, s);
+  return device_add(r, ring_put_particles_kernel, a, grid, a.n, a.new_size, stream);
 }
 
 // The checks of an rb_hindsight that need no ring (made before the handle is looked at).
@@ -864,14 +848,9 @@ int rb_add_device_hindsight(rb_handle* h, const float* state, const float* actio
   for (int a = 0; a < hs->g; ++a) TD3_ARG(hs->cols[a] < r->sd, "hs->cols must be below state_dim");
   if (n == 0) return 0;
   TD3_ARG(state && action && next_state && reward && done, "null input");
-  TD3_HIP(hipSetDevice(r->device));
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  TD3_RC(ring_begin_write(r, s));
   const RingPutDeviceHsArgs a{ring_put_device_args(r, state, action, next_state, reward, done, n * (1 + hs->k)),
                               hindsight_args(hs)};
-  hipLaunchKernelGGL(ring_put_device_hs_kernel, dim3(ring_put_device_grid(a.p)), dim3(256), 0, s, a);
-  TD3_HIP(hipGetLastError());
-  return ring_wrote(r, a.p.n, a.p.new_size, s);
+  return device_add(r, ring_put_device_hs_kernel, a, ring_put_device_grid(a.p), a.p.n, a.p.new_size, stream);
 }
 
 int rb_add_particles_device_hindsight(rb_handle* h, const float* feat, const float* part, const float* action,
@@ -885,18 +864,13 @@ int rb_add_particles_device_hindsight(rb_handle* h, const float* feat, const flo
   for (int a = 0; a < hs->g; ++a) TD3_ARG(hs->cols[a] < r->sd, "hs->cols must be below feat_dim");
   if (n == 0) return 0;
   TD3_ARG(feat && part && action && next_feat && next_part && reward && done, "null input");
-  TD3_HIP(hipSetDevice(r->device));
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  TD3_RC(ring_begin_write(r, s));
   const int copies = 1 + hs->k;
   const RingPutPartHsArgs a{
-      ring_put_part_args(r, feat, part, action, next_feat, next_part, reward, done, n * copies),
+      ring_put_part_args(r, {feat, part, action, next_feat, next_part, reward, done}, n * copies),
       hindsight_args(hs), r->o_s, r->o_s2, r->o_r, r->sd};
   const int64_t src_rows = n - a.p.skip / copies;          // source transitions with a surviving copy
   const int grid = (int)std::min<int64_t>(src_rows * a.p.ntile, 4096);
-  hipLaunchKernelGGL(ring_put_particles_hs_kernel, dim3(grid), dim3(256), 0, s, a);
-  TD3_HIP(hipGetLastError());
-  return ring_wrote(r, a.p.n, a.p.new_size, s);
+  return device_add(r, ring_put_particles_hs_kernel, a, grid, a.p.n, a.p.new_size, stream);
 }
 
 int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, void* stream) {
@@ -913,11 +887,28 @@ int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, 
                        r->ptr, n, r->cap, max_action, seed);
     TD3_HIP(hipGetLastError());
   }
-  r->ptr = (r->ptr + n) % r->cap;
-  r->size = std::min<int64_t>(r->size + n, r->cap);
-  hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, s, r->d_size, r->size);
+  const int64_t new_size = std::min<int64_t>(r->size + n, r->cap);
+  hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, s, r->d_size, new_size);
   TD3_HIP(hipGetLastError());
-  return ring_end_write(r, s);
+  return ring_wrote(r, n, new_size, s);
+}
+
+// The stand-alone sample of either kind: field k of the drawn records into out[k] ([batch][field[k].len]).
+static int sample_fields(Ring* r, float* const out[], int batch, const int64_t* inject_idx, int64_t* idx_out,
+                         void* stream) {
+  TD3_HIP(hipSetDevice(r->device));
+  GatherArgs a = gather_base(r);
+  for (int k = 0; k < r->nfield; ++k) a.seg[k] = GatherSeg{out[k], r->field[k].len, 0, r->field[k].off, r->field[k].len};
+  a.nseg = r->nfield;
+  a.B = a.Bp = batch;
+  a.inject_idx = inject_idx;
+  a.idx_out = idx_out;
+  a.ctr = nullptr;
+  a.step = ++r->sample_calls;
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_read(r, s));                     // add() before sample() (main.py:261, :269)
+  TD3_RC(launch_gather(a, s));
+  return ring_end_read(r, s);
 }
 
 int rb_sample(rb_handle* h, int batch, float* state, float* action, float* next_state,
@@ -929,27 +920,8 @@ int rb_sample(rb_handle* h, int batch, float* state, float* action, float* next_
   TD3_ARG(batch >= 0, "batch must be >= 0");
   TD3_ARG(r->size > 0 || batch == 0 || inject_idx, "sample from an empty buffer");
   TD3_ARG(state && action && next_state && reward && not_done, "null output");
-  TD3_HIP(hipSetDevice(r->device));
-  GatherArgs a{};
-  a.seg[0] = GatherSeg{state, r->sd, 0, r->o_s, r->sd};
-  a.seg[1] = GatherSeg{action, r->ad, 0, r->o_a, r->ad};
-  a.seg[2] = GatherSeg{next_state, r->sd, 0, r->o_s2, r->sd};
-  a.seg[3] = GatherSeg{reward, 1, 0, r->o_r, 1};
-  a.seg[4] = GatherSeg{not_done, 1, 0, r->o_nd, 1};
-  a.nseg = 5;
-  a.B = a.Bp = batch;
-  a.data = r->data;
-  a.rec = r->rec;
-  a.d_size = r->d_size;
-  a.inject_idx = inject_idx;
-  a.idx_out = idx_out;
-  a.seed = r->seed;
-  a.ctr = nullptr;
-  a.step = ++r->sample_calls;
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  TD3_RC(ring_begin_read(r, s));                     // add() before sample() (main.py:261, :269)
-  TD3_RC(launch_gather(a, s));
-  return ring_end_read(r, s);
+  float* const out[] = {state, action, next_state, reward, not_done};
+  return sample_fields(r, out, batch, inject_idx, idx_out, stream);
 }
 
 int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float* action, float* next_feat,
@@ -961,30 +933,8 @@ int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float
   TD3_ARG(batch >= 0, "batch must be >= 0");
   TD3_ARG(r->size > 0 || batch == 0 || inject_idx, "sample from an empty buffer");
   TD3_ARG(feat && part && action && next_feat && next_part && reward && not_done, "null output");
-  TD3_HIP(hipSetDevice(r->device));
-  const int np = r->N * r->D;
-  GatherArgs a{};
-  a.seg[0] = GatherSeg{feat, r->sd, 0, r->o_s, r->sd};
-  a.seg[1] = GatherSeg{part, np, 0, r->o_p, np};
-  a.seg[2] = GatherSeg{action, r->ad, 0, r->o_a, r->ad};
-  a.seg[3] = GatherSeg{next_feat, r->sd, 0, r->o_s2, r->sd};
-  a.seg[4] = GatherSeg{next_part, np, 0, r->o_p2, np};
-  a.seg[5] = GatherSeg{reward, 1, 0, r->o_r, 1};
-  a.seg[6] = GatherSeg{not_done, 1, 0, r->o_nd, 1};
-  a.nseg = 7;
-  a.B = a.Bp = batch;
-  a.data = r->data;
-  a.rec = r->rec;
-  a.d_size = r->d_size;
-  a.inject_idx = inject_idx;
-  a.idx_out = idx_out;
-  a.seed = r->seed;
-  a.ctr = nullptr;
-  a.step = ++r->sample_calls;
-  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
-  TD3_RC(ring_begin_read(r, s));                     // add() before sample() (main.py:261, :269)
-  TD3_RC(launch_gather(a, s));
-  return ring_end_read(r, s);
+  float* const out[] = {feat, part, action, next_feat, next_part, reward, not_done};
+  return sample_fields(r, out, batch, inject_idx, idx_out, stream);
 }
 
 int rb_read_records(const rb_handle* h, int64_t start, int64_t n, float* out) {

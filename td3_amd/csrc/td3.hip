@@ -2228,9 +2228,20 @@ static int run_stages_probed(td3_handle* h, std::vector<Stage>& st, hipStream_t 
 // Input stage: Philox index draw + gather from the ring into the padded batch buffers.
 static int input_from_ring_particles(td3_handle* h, Ring* r, Plan* P, bool inject_idx, hipStream_t s);
 
+// A step's gather without its segments: the plan's batch, the rows drawn by the step counter.
+static GatherArgs step_gather(const td3_handle* h, const Ring* r, const Plan* P, bool inject_idx) {
+  GatherArgs a = gather_base(r);
+  a.B = P->B;
+  a.Bp = P->Bp;
+  a.inject_idx = inject_idx ? P->d_inject_idx : nullptr;
+  a.idx_out = P->d_idx;
+  a.ctr = h->d_ctr;
+  return a;
+}
+
 static int input_from_ring(td3_handle* h, Ring* r, Plan* P, bool inject_idx, hipStream_t s) {
   if (P->particles) return input_from_ring_particles(h, r, P, inject_idx, s);
-  GatherArgs a{};
+  GatherArgs a = step_gather(h, r, P, inject_idx);
   const int sd = h->sd, ad = h->ad;
   int k = 0;
   // s once per network input that holds it ([s | a] and [s | pi(s)]), s' once ([s' | a']): the
@@ -2242,22 +2253,13 @@ static int input_from_ring(td3_handle* h, Ring* r, Plan* P, bool inject_idx, hip
   a.seg[k++] = GatherSeg{P->R, 1, 0, r->o_r, 1};
   a.seg[k++] = GatherSeg{P->ND, 1, 0, r->o_nd, 1};
   a.nseg = k;
-  a.B = P->B;
-  a.Bp = P->Bp;
-  a.data = r->data;
-  a.rec = r->rec;
-  a.d_size = r->d_size;
-  a.inject_idx = inject_idx ? P->d_inject_idx : nullptr;
-  a.idx_out = P->d_idx;
-  a.seed = r->seed;
-  a.ctr = h->d_ctr;
   return launch_gather(a, s);
 }
 
 // Particle rings: the small fields go to every network's MLP input rows; the particle blocks
 // stay in the ring and are read there by the encoders (rows P->d_idx).
 static int input_from_ring_particles(td3_handle* h, Ring* r, Plan* P, bool inject_idx, hipStream_t s) {
-  GatherArgs a{};
+  GatherArgs a = step_gather(h, r, P, inject_idx);
   const int F = h->sd, ad = h->ad, c0 = kEncC2;
   const bool cdq = h->cdq != 0;
   int k = 0;
@@ -2272,15 +2274,6 @@ static int input_from_ring_particles(td3_handle* h, Ring* r, Plan* P, bool injec
   a.seg[k++] = GatherSeg{P->R, 1, 0, r->o_r, 1};
   a.seg[k++] = GatherSeg{P->ND, 1, 0, r->o_nd, 1};
   a.nseg = k;
-  a.B = P->B;
-  a.Bp = P->Bp;
-  a.data = r->data;
-  a.rec = r->rec;
-  a.d_size = r->d_size;
-  a.inject_idx = inject_idx ? P->d_inject_idx : nullptr;
-  a.idx_out = P->d_idx;
-  a.seed = r->seed;
-  a.ctr = h->d_ctr;
   return launch_gather(a, s);
 }
 

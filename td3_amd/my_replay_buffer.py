@@ -55,22 +55,6 @@ def _is_cuda_tensor(x) -> bool:
     return bool(getattr(x, "is_cuda", False))
 
 
-def _new_stage(buf, rows):
-    """Host records staged by ``add`` (zeroed: the record pad stays 0) and their float*."""
-    buf._stage = np.zeros((rows, buf.record_floats), dtype=np.float32)
-    buf._stage_ptr = _lib.fptr(buf._stage)
-    buf._n = 0
-
-
-def _flush_stage(buf, stream=None):
-    """Ship the staged records; ``stream`` (a learner's, from ``TD3.train``) queues them in that
-    stream's order, so the step that samples them needs no cross-stream event (replay.h)."""
-    n = buf._n
-    if n:
-        buf._n = 0
-        check(buf._lib.rb_add_records(buf._h, buf._stage_ptr, n, stream), "rb_add_records")
-
-
 def _device_rows(dev, arrays, widths, what):
     """The inputs of a device add as contiguous fp32 tensors on ``dev`` (``[n][w]``, ``[n]`` where
     the width is 0) and their common row count n; a ValueError naming ``what`` when the counts differ."""
@@ -204,10 +188,17 @@ def _load_int(path):
     return int(v)
 
 
-class ReplayBuffer_featured(object):
-    """Flat-observation replay ring (my_replay_buffer.py:72-128) resident in HBM."""
+class _RingBuffer(object):
+    """What the two ring kinds share: the handle, the records staged by ``add``, the batch adds,
+    ``sample`` and ``save`` / ``load``.  All of it walks one field table, ``_fields``, built in
+    ``_create``: per ``store_np`` array its name, flat width and per-row shape, in record order
+    (replay.h: the fields lie one behind the other from column 0; the last one is not_done).
 
-    store_np = ["state", "action", "next_state", "reward", "not_done"]
+    A kind supplies ``store_np``, its reading of ``obs_space``, ``_dims`` / ``_row_shapes`` /
+    ``_dims_from``, the names of its C calls (``_C``), how its inputs are counted in messages
+    (``_count``), the fields hindsight relabels (``_relabel``: the two states, the reward), the length
+    of its stage and the public ``add`` / ``add_batch`` / ``add_batch_hindsight`` signatures."""
+
     store_pkl = ["ptr", "size"]
 
     def __init__(self, obs_space, action_space, max_size=int(1e6), load_folder=None,
@@ -215,8 +206,7 @@ class ReplayBuffer_featured(object):
         self._lib = _lib.load()
         self.host_shadow = bool(host_shadow)
         self._shadow = None
-        self.state_dim = int(obs_space.shape[0])
-        self.action_dim = int(action_space.shape[0])
+        self._read_spaces(obs_space, action_space)
         self._dev = default_device_index() if device is None else int(device)
         torch = _torch()
         self.device = torch.device("cuda", self._dev)
@@ -229,29 +219,33 @@ class ReplayBuffer_featured(object):
             self._create(int(max_size))
 
     # ------------------------------------------------------------------ plumbing
+    def _call(self, name, *args):
+        check(getattr(self._lib, name)(*args), name)
+
     def _create(self, max_size):
         import ctypes as C
         if self._h is not None:
             self._lib.rb_destroy(self._h)
             self._h = None
         h = C.c_void_p()
-        check(self._lib.rb_create(self.state_dim, self.action_dim, max_size, self._dev,
-                                  self.seed, C.byref(h)), "rb_create")
+        self._call(self._C["create"], *self._dims(), max_size, self._dev, self.seed, C.byref(h))
         self._h = h
         self.max_size = max_size
-        info = self._info()
-        self.record_floats = info.record_floats
-        _new_stage(self, _STAGE_ROWS)
-        sd, ad = self.state_dim, self.action_dim
-        # replay.h record: [ s | a | s' | r | not_done | pad ]
-        self._cols = (slice(0, sd), slice(sd, sd + ad), slice(sd + ad, 2 * sd + ad),
-                      slice(2 * sd + ad, 2 * sd + ad + 1), slice(2 * sd + ad + 1, 2 * sd + ad + 2))
+        self.record_floats = self._info().record_floats
+        self._fields = tuple((name, int(np.prod(shape)), tuple(shape))
+                             for name, shape in zip(self.store_np, self._row_shapes()))
+        widths = [w for _, w, _ in self._fields]
+        assert self.record_floats == (sum(widths) + 3) // 4 * 4, "field table out of step with rb_info"
+        self._cols = tuple(slice(sum(widths[:k]), sum(widths[:k + 1])) for k in range(len(widths)))
+        self._widths = tuple(widths[:-2]) + (0, 0)   # of the add inputs: reward and done are [n]
+        # host records staged by ``add`` (zeroed: the record pad stays 0) and their float*
+        self._stage = np.zeros((self._stage_rows, self.record_floats), dtype=np.float32)
+        self._stage_ptr = _lib.fptr(self._stage)
+        self._n = 0
         self._shadow = _HostShadow.zeros(self._shapes(max_size)) if self.host_shadow else None
 
     def _shapes(self, n):
-        sd, ad = self.state_dim, self.action_dim
-        return {"state": (n, sd), "action": (n, ad), "next_state": (n, sd), "reward": (n, 1),
-                "not_done": (n, 1)}
+        return {name: (n, *shape) for name, _, shape in self._fields}
 
     def _info(self):
         info = _lib.rb_info_t()
@@ -278,7 +272,170 @@ class ReplayBuffer_featured(object):
     def _torch_order(self):
         return _TorchOrder(self._lib.rb_stream(self._h), self.device)
 
-    # ------------------------------------------------------------------ reference API
+    def flush(self, stream=None):
+        """Ship the staged records; ``stream`` (a learner's, from ``TD3.train``) queues them in that
+        stream's order, so the step that samples them needs no cross-stream event (replay.h)."""
+        n = self._n
+        if n:
+            self._n = 0
+            check(self._lib.rb_add_records(self._h, self._stage_ptr, n, stream), "rb_add_records")
+
+    # ------------------------------------------------------------------ batch adds
+    def _add_batch(self, *arrays):
+        self.flush()
+        if _is_cuda_tensor(arrays[0]):
+            self._add_batch_device(*arrays)
+            return
+        first = np.ascontiguousarray(arrays[0], dtype=np.float64).reshape(-1, self._widths[0])
+        n = first.shape[0]
+        arrs = [first] + [np.ascontiguousarray(x, dtype=np.float64).reshape((n, w) if w else (n,))
+                          for x, w in zip(arrays[1:], self._widths[1:])]
+        if self._shadow is not None:
+            self._shadow.put_batch(arrs[:-1] + [1. - arrs[-1]], n)
+        self._call(self._C["add"], self._h, *[_lib.dptr(x) for x in arrs], n, self._stream())
+
+    def _add_batch_device(self, *arrays):
+        ts, n = _device_rows(self.device, arrays, self._widths, f"add_batch: the {self._count} inputs")
+        if self._shadow is not None:
+            self._shadow.valid = False           # rows the host never saw: save() writes the ring
+        # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
+        # the blocks freed with them are reused only after the add read them
+        with self._torch_order():
+            self._call(self._C["add_device"], self._h, *[t.data_ptr() for t in ts], n, self._stream())
+
+    def _add_batch_hindsight(self, arrays, goal_cols, goals, rewards):
+        self.flush()
+        what = f"add_batch_hindsight: the {self._count} inputs"
+        if _is_cuda_tensor(arrays[0]):
+            ts, n = _device_rows(self.device, arrays, self._widths, what)
+            hs, keep = _hindsight_device(self.device, goal_cols, goals, rewards, n)
+            if n == 0:
+                return
+            if self._shadow is not None:
+                self._shadow.valid = False       # rows the host never saw: save() writes the ring
+            with self._torch_order():            # as _add_batch_device; `keep` lives until the exit
+                self._call(self._C["add_device_hindsight"], self._h, *[t.data_ptr() for t in ts], n, hs,
+                           self._stream())
+            return
+        arrs = [np.ascontiguousarray(arrays[0], dtype=np.float64).reshape(-1, self._widths[0])]
+        arrs += [np.asarray(x, dtype=np.float64).reshape((-1, w) if w else (-1,))
+                 for x, w in zip(arrays[1:], self._widths[1:])]
+        n = arrs[0].shape[0]
+        if any(x.shape[0] != n for x in arrs):
+            raise ValueError(f"{what} must have the same number of rows")
+        goals, rewards = np.asarray(goals), np.asarray(rewards)
+        cols, K, _ = _hindsight_dims(goal_cols, goals, rewards, n)
+        if n:
+            self.add_batch(*_hindsight_expand(arrs, *self._relabel, cols, K, goals, rewards))
+
+    def fill_synthetic(self, n, max_action=1.0, seed=0):
+        """Device-side prefill with the SURVEY §8(d) synthetic distribution (bench/tests)."""
+        self.flush()
+        if self._shadow is not None:
+            self._shadow.valid = False           # rows the host never saw: save() writes the ring
+        check(self._lib.rb_fill_synthetic(self._h, int(n), float(max_action), int(seed),
+                                          self._stream()), "rb_fill_synthetic")
+
+    def sample(self, batch_size, indices=None, return_indices=False):
+        """my_replay_buffer.py:119-128 / :58-69: the ``store_np`` fields of the drawn rows, fp32 on
+        the device (5 tensors, or 7 with the particle blocks as ``[B][N][D]``)."""
+        torch = _torch()
+        self.flush()
+        B = int(batch_size)
+        dev = self.device
+        out = tuple(torch.empty((B, *shape), device=dev, dtype=torch.float32) for _, _, shape in self._fields)
+        idx_out = torch.empty((B,), device=dev, dtype=torch.int64)
+        inj = None
+        if indices is not None:
+            inj = torch.as_tensor(np.asarray(indices, dtype=np.int64), device=dev)
+            if inj.numel() != B:
+                raise ValueError("indices must have batch_size entries")
+            size = self.size
+            if B and (int(inj.min()) < 0 or int(inj.max()) >= max(size, 1)):
+                raise IndexError("index out of range of the filled buffer")
+        with self._torch_order():
+            self._call(self._C["sample"], self._h, B, *[t.data_ptr() for t in out],
+                       inj.data_ptr() if inj is not None else None, idx_out.data_ptr(), self._stream())
+        if return_indices:
+            return out, idx_out
+        return out
+
+    # ------------------------------------------------------------------ persistence
+    def _records(self):
+        n = self.max_size
+        rec = np.empty((n, self.record_floats), dtype=np.float32)
+        check(self._lib.rb_read_records(self._h, 0, n, _lib.fptr(rec)), "rb_read_records")
+        return rec
+
+    def save(self, folder):
+        """my_replay_buffer.py:91-99 / :24-32: ptr/size pickled (protocol 4), arrays via np.save (the
+        float64 host shadow when kept, else the fp32 ring widened)."""
+        self.flush()
+        info = self._info()
+        sh = self._shadow
+        if sh is not None and sh.valid:
+            assert sh.ptr == int(info.ptr) % sh.cap, "host shadow out of step with the ring"
+            arrays = sh.arrays
+        else:
+            rec = self._records()
+            arrays = {name: rec[:, c].astype(np.float64).reshape((self.max_size, *shape))
+                      for (name, _, shape), c in zip(self._fields, self._cols)}
+        _save_folder(folder, info.ptr, info.size, arrays)
+
+    def load(self, folder):
+        """my_replay_buffer.py:101-107 / :34-44 (pickles are read by an int-only unpickler)."""
+        self._n = 0                         # rows added before a load are replaced with it
+        ptr = _load_int(os.path.join(folder, "ptr.pkl"))
+        size = _load_int(os.path.join(folder, "size.pkl"))
+        arrs = {}
+        for attrib in self.store_np:
+            with open(os.path.join(folder, attrib + ".pkl"), "rb") as f:
+                arrs[attrib] = np.load(f, allow_pickle=False)
+        n = arrs[self.store_np[0]].shape[0]
+        self._dims_from(arrs)
+        self._create(n)
+        if self.host_shadow:                     # the loaded arrays themselves, bytes untouched
+            self._shadow = _HostShadow(arrs, ptr)
+        rec = np.zeros((n, self.record_floats), dtype=np.float32)
+        for (name, w, _), c in zip(self._fields, self._cols):
+            rec[:, c] = arrs[name].reshape(n, w)
+        check(self._lib.rb_write_records(self._h, 0, n, _lib.fptr(rec), ptr % n, min(size, n)),
+              "rb_write_records")
+
+    def __del__(self):
+        try:
+            if self._h is not None and _lib.alive():
+                self._lib.rb_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class ReplayBuffer_featured(_RingBuffer):
+    """Flat-observation replay ring (my_replay_buffer.py:72-128) resident in HBM."""
+
+    store_np = ["state", "action", "next_state", "reward", "not_done"]
+    _C = {"create": "rb_create", "add": "rb_add", "add_device": "rb_add_device",
+          "add_device_hindsight": "rb_add_device_hindsight", "sample": "rb_sample"}
+    _count = "five"
+    _relabel = ((0, 2), 3)
+    _stage_rows = _STAGE_ROWS
+
+    def _read_spaces(self, obs_space, action_space):
+        self.state_dim = int(obs_space.shape[0])
+        self.action_dim = int(action_space.shape[0])
+
+    def _dims(self):
+        return self.state_dim, self.action_dim
+
+    def _row_shapes(self):
+        sd, ad = self._dims()
+        return (sd,), (ad,), (sd,), (1,), (1,)
+
+    def _dims_from(self, arrs):
+        self.state_dim = arrs["state"].shape[1]
+        self.action_dim = arrs["action"].shape[1]
+
     def add(self, state, action, next_state, reward, done):
         """my_replay_buffer.py:109-117 (stores not_done = 1 - done): numpy row assignment as the
         reference's, into the staged fp32 record."""
@@ -299,34 +456,7 @@ class ReplayBuffer_featured(object):
         """Bulk add of n transitions (experience_injection.py / hindsight relabel path).  Torch
         CUDA tensors (a GPU-resident environment's rows, any float dtype) go from device memory
         straight into the ring (``rb_add_device``): no host copy, no synchronisation."""
-        self.flush()
-        if _is_cuda_tensor(state):
-            self._add_batch_device(state, action, next_state, reward, done)
-            return
-        s = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, self.state_dim)
-        n = s.shape[0]
-        a = np.ascontiguousarray(action, dtype=np.float64).reshape(n, self.action_dim)
-        s2 = np.ascontiguousarray(next_state, dtype=np.float64).reshape(n, self.state_dim)
-        r = np.ascontiguousarray(reward, dtype=np.float64).reshape(n)
-        d = np.ascontiguousarray(done, dtype=np.float64).reshape(n)
-        if self._shadow is not None:
-            self._shadow.put_batch((s, a, s2, r, 1. - d), n)
-        check(self._lib.rb_add(self._h, _lib.dptr(s), _lib.dptr(a), _lib.dptr(s2), _lib.dptr(r),
-                               _lib.dptr(d), n, self._stream()), "rb_add")
-
-    def _device_rows(self, arrays, what):
-        sd, ad = self.state_dim, self.action_dim
-        return _device_rows(self.device, arrays, (sd, ad, sd, 0, 0), what)
-
-    def _add_batch_device(self, *arrays):
-        ts, n = self._device_rows(arrays, "add_batch: the five inputs")
-        if self._shadow is not None:
-            self._shadow.valid = False           # rows the host never saw: save() writes the ring
-        # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
-        # the blocks freed with them are reused only after the add read them
-        with self._torch_order():
-            check(self._lib.rb_add_device(self._h, *[t.data_ptr() for t in ts], n, self._stream()),
-                  "rb_add_device")
+        self._add_batch(state, action, next_state, reward, done)
 
     def add_batch_hindsight(self, state, action, next_state, reward, done, *, goal_cols, goals, rewards):
         """``add_to_replay_buffer`` with K hindsight relabels per transition (main.py:70-91) for n
@@ -336,137 +466,10 @@ class ReplayBuffer_featured(object):
         ``rewards[i][j]`` (``[n][K]``) as the reward.  Exactly ``add_batch`` of those n * (1 + K)
         rows.  CUDA tensors are fanned out by the add kernel itself (``rb_add_device_hindsight``:
         no expanded copy is made); host arrays are expanded in float64 and take the host add."""
-        self.flush()
-        if _is_cuda_tensor(state):
-            ts, n = self._device_rows((state, action, next_state, reward, done),
-                                       "add_batch_hindsight: the five inputs")
-            hs, keep = _hindsight_device(self.device, goal_cols, goals, rewards, n)
-            if n == 0:
-                return
-            if self._shadow is not None:
-                self._shadow.valid = False       # rows the host never saw: save() writes the ring
-            with self._torch_order():            # as _add_batch_device; `keep` lives until the exit
-                check(self._lib.rb_add_device_hindsight(self._h, *[t.data_ptr() for t in ts], n, hs,
-                                                        self._stream()), "rb_add_device_hindsight")
-            return
-        s = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, self.state_dim)
-        n = s.shape[0]
-        arrs = [s, np.asarray(action, dtype=np.float64).reshape(-1, self.action_dim),
-                np.asarray(next_state, dtype=np.float64).reshape(-1, self.state_dim),
-                np.asarray(reward, dtype=np.float64).reshape(-1), np.asarray(done, dtype=np.float64).reshape(-1)]
-        if any(x.shape[0] != n for x in arrs):
-            raise ValueError("add_batch_hindsight: the five inputs must have the same number of rows")
-        goals, rewards = np.asarray(goals), np.asarray(rewards)
-        cols, K, _ = _hindsight_dims(goal_cols, goals, rewards, n)
-        if n:
-            self.add_batch(*_hindsight_expand(arrs, (0, 2), 3, cols, K, goals, rewards))
-
-    def flush(self, stream=None):
-        _flush_stage(self, stream)
-
-    def fill_synthetic(self, n, max_action=1.0, seed=0):
-        """Device-side prefill with the SURVEY §8(d) synthetic distribution (bench/tests)."""
-        self.flush()
-        if self._shadow is not None:
-            self._shadow.valid = False           # rows the host never saw: save() writes the ring
-        check(self._lib.rb_fill_synthetic(self._h, int(n), float(max_action), int(seed),
-                                          self._stream()), "rb_fill_synthetic")
-
-    def sample(self, batch_size, indices=None, return_indices=False):
-        """my_replay_buffer.py:119-128: (state, action, next_state, reward, not_done) fp32 on device."""
-        torch = _torch()
-        self.flush()
-        B = int(batch_size)
-        dev = self.device
-        out = (torch.empty((B, self.state_dim), device=dev, dtype=torch.float32),
-               torch.empty((B, self.action_dim), device=dev, dtype=torch.float32),
-               torch.empty((B, self.state_dim), device=dev, dtype=torch.float32),
-               torch.empty((B, 1), device=dev, dtype=torch.float32),
-               torch.empty((B, 1), device=dev, dtype=torch.float32))
-        idx_out = torch.empty((B,), device=dev, dtype=torch.int64)
-        inj = None
-        if indices is not None:
-            inj = torch.as_tensor(np.asarray(indices, dtype=np.int64), device=dev)
-            if inj.numel() != B:
-                raise ValueError("indices must have batch_size entries")
-            size = self.size
-            if B and (int(inj.min()) < 0 or int(inj.max()) >= max(size, 1)):
-                raise IndexError("index out of range of the filled buffer")
-        with self._torch_order():
-            check(self._lib.rb_sample(self._h, B, *[t.data_ptr() for t in out],
-                                      inj.data_ptr() if inj is not None else None,
-                                      idx_out.data_ptr(), self._stream()), "rb_sample")
-        if return_indices:
-            return out, idx_out
-        return out
-
-    # ------------------------------------------------------------------ persistence
-    def _records(self):
-        n = self.max_size
-        rec = np.empty((n, self.record_floats), dtype=np.float32)
-        check(self._lib.rb_read_records(self._h, 0, n, _lib.fptr(rec)), "rb_read_records")
-        return rec
-
-    def _arrays(self):
-        rec = self._records()
-        sd, ad = self.state_dim, self.action_dim
-        return {
-            "state": rec[:, :sd].astype(np.float64),
-            "action": rec[:, sd:sd + ad].astype(np.float64),
-            "next_state": rec[:, sd + ad:2 * sd + ad].astype(np.float64),
-            "reward": rec[:, 2 * sd + ad:2 * sd + ad + 1].astype(np.float64),
-            "not_done": rec[:, 2 * sd + ad + 1:2 * sd + ad + 2].astype(np.float64),
-        }
-
-    def _saved_arrays(self, info):
-        sh = self._shadow
-        if sh is not None and sh.valid:
-            assert sh.ptr == int(info.ptr) % sh.cap, "host shadow out of step with the ring"
-            return sh.arrays
-        return self._arrays()
-
-    def save(self, folder):
-        """my_replay_buffer.py:91-99: ptr/size pickled (protocol 4), arrays via np.save (the float64
-        host shadow when kept, else the fp32 ring widened)."""
-        self.flush()
-        info = self._info()
-        _save_folder(folder, info.ptr, info.size, self._saved_arrays(info))
-
-    def load(self, folder):
-        """my_replay_buffer.py:101-107 (pickles are read by an int-only unpickler)."""
-        self._n = 0                         # rows added before a load are replaced with it
-        ptr = _load_int(os.path.join(folder, "ptr.pkl"))
-        size = _load_int(os.path.join(folder, "size.pkl"))
-        arrs = {}
-        for attrib in self.store_np:
-            with open(os.path.join(folder, attrib + ".pkl"), "rb") as f:
-                arrs[attrib] = np.load(f, allow_pickle=False)
-        n = arrs["state"].shape[0]
-        self.state_dim = arrs["state"].shape[1]
-        self.action_dim = arrs["action"].shape[1]
-        self._create(n)
-        if self.host_shadow:                     # the loaded arrays themselves, bytes untouched
-            self._shadow = _HostShadow(arrs, ptr)
-        sd, ad = self.state_dim, self.action_dim
-        rec = np.zeros((n, self.record_floats), dtype=np.float32)
-        rec[:, :sd] = arrs["state"]
-        rec[:, sd:sd + ad] = arrs["action"]
-        rec[:, sd + ad:2 * sd + ad] = arrs["next_state"]
-        rec[:, 2 * sd + ad] = arrs["reward"].reshape(n)
-        rec[:, 2 * sd + ad + 1] = arrs["not_done"].reshape(n)
-        check(self._lib.rb_write_records(self._h, 0, n, _lib.fptr(rec), ptr % n, min(size, n)),
-              "rb_write_records")
-
-    def __del__(self):
-        try:
-            if self._h is not None and _lib.alive():
-                self._lib.rb_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._add_batch_hindsight((state, action, next_state, reward, done), goal_cols, goals, rewards)
 
 
-class ReplayBuffer_particles(object):
+class ReplayBuffer_particles(_RingBuffer):
     """Particle-observation replay ring (my_replay_buffer.py:6-69) resident in HBM.
 
     ``obs_space`` is the reference's 2-tuple of Boxes: features ``[F]`` and particles
@@ -477,78 +480,29 @@ class ReplayBuffer_particles(object):
 
     store_np = ["state_features", "state_particles", "action", "next_state_features",
                 "next_state_particles", "reward", "not_done"]
-    store_pkl = ["ptr", "size"]
+    _C = {"create": "rb_create_particles", "add": "rb_add_particles", "add_device": "rb_add_particles_device",
+          "add_device_hindsight": "rb_add_particles_device_hindsight", "sample": "rb_sample_particles"}
+    _count = "seven"
+    _relabel = ((0, 3), 5)
+    _stage_rows = max(1, _STAGE_ROWS // 16)
 
-    def __init__(self, obs_space, action_space, max_size=int(1e6), load_folder=None,
-                 device=None, seed=0, host_shadow=False):
-        self._lib = _lib.load()
-        self.host_shadow = bool(host_shadow)
-        self._shadow = None
+    def _read_spaces(self, obs_space, action_space):
         self.feat_dim = int(obs_space[0].shape[0])
         self.n_particles, self.particle_dim = (int(x) for x in obs_space[1].shape)
         self.action_dim = int(action_space.shape[0])
-        self._dev = default_device_index() if device is None else int(device)
-        torch = _torch()
-        self.device = torch.device("cuda", self._dev)
-        self.seed = int(seed)
-        self._h = None
-        self._n = 0
-        if load_folder is not None:
-            self.load(load_folder)
-        else:
-            self._create(int(max_size))
 
-    def _create(self, max_size):
-        import ctypes as C
-        if self._h is not None:
-            self._lib.rb_destroy(self._h)
-            self._h = None
-        h = C.c_void_p()
-        check(self._lib.rb_create_particles(self.feat_dim, self.n_particles, self.particle_dim,
-                                            self.action_dim, max_size, self._dev, self.seed,
-                                            C.byref(h)), "rb_create_particles")
-        self._h = h
-        self.max_size = max_size
-        self.record_floats = self._info().record_floats
-        _new_stage(self, max(1, _STAGE_ROWS // 16))
-        self._cols = tuple(slice(c, c + w) for c, w in self._offsets().values())
-        self._shadow = _HostShadow.zeros(self._shapes(max_size)) if self.host_shadow else None
+    def _dims(self):
+        return self.feat_dim, self.n_particles, self.particle_dim, self.action_dim
 
-    def _shapes(self, n):
-        F, A, nd = self.feat_dim, self.action_dim, (self.n_particles, self.particle_dim)
-        return {"state_features": (n, F), "state_particles": (n, *nd), "action": (n, A),
-                "next_state_features": (n, F), "next_state_particles": (n, *nd), "reward": (n, 1),
-                "not_done": (n, 1)}
+    def _row_shapes(self):
+        F, N, D, A = self._dims()
+        return (F,), (N, D), (A,), (F,), (N, D), (1,), (1,)
 
-    def _info(self):
-        info = _lib.rb_info_t()
-        check(self._lib.rb_info(self._h, info), "rb_info")
-        return info
+    def _dims_from(self, arrs):
+        self.feat_dim = arrs["state_features"].shape[1]
+        self.n_particles, self.particle_dim = arrs["state_particles"].shape[1:3]
+        self.action_dim = arrs["action"].shape[1]
 
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def ptr(self):
-        self.flush()
-        return int(self._info().ptr)
-
-    @property
-    def size(self):
-        self.flush()
-        return int(self._info().size)
-
-    def _stream(self):
-        return None
-
-    def _torch_order(self):
-        return _TorchOrder(self._lib.rb_stream(self._h), self.device)
-
-    def _np(self):
-        return self.n_particles * self.particle_dim
-
-    # ------------------------------------------------------------------ reference API
     def add(self, state, action, next_state, reward, done):
         """my_replay_buffer.py:46-56 (state = (features, particles); stores 1 - done)."""
         row = self._stage[self._n]
@@ -571,37 +525,7 @@ class ReplayBuffer_particles(object):
         """Bulk add of n transitions.  Torch CUDA tensors (a GPU-resident environment's rows, any
         float dtype; particles ``[n][N][D]`` or ``[n][N*D]``) go from device memory straight into
         the ring (``rb_add_particles_device``): no host copy, no synchronisation."""
-        self.flush()
-        if _is_cuda_tensor(feat):
-            self._add_batch_device(feat, part, action, next_feat, next_part, reward, done)
-            return
-        F, npd, A = self.feat_dim, self._np(), self.action_dim
-        f = np.ascontiguousarray(feat, dtype=np.float64).reshape(-1, F)
-        n = f.shape[0]
-        arrs = [f, np.ascontiguousarray(part, dtype=np.float64).reshape(n, npd),
-                np.ascontiguousarray(action, dtype=np.float64).reshape(n, A),
-                np.ascontiguousarray(next_feat, dtype=np.float64).reshape(n, F),
-                np.ascontiguousarray(next_part, dtype=np.float64).reshape(n, npd),
-                np.ascontiguousarray(reward, dtype=np.float64).reshape(n),
-                np.ascontiguousarray(done, dtype=np.float64).reshape(n)]
-        if self._shadow is not None:
-            self._shadow.put_batch(arrs[:6] + [1. - arrs[6]], n)
-        check(self._lib.rb_add_particles(self._h, *[_lib.dptr(x) for x in arrs], n, self._stream()),
-              "rb_add_particles")
-
-    def _device_rows(self, arrays, what):
-        F, npd, A = self.feat_dim, self._np(), self.action_dim
-        return _device_rows(self.device, arrays, (F, npd, A, F, npd, 0, 0), what)
-
-    def _add_batch_device(self, *arrays):
-        ts, n = self._device_rows(arrays, "add_batch: the seven inputs")
-        if self._shadow is not None:
-            self._shadow.valid = False           # rows the host never saw: save() writes the ring
-        # the tensors were made on torch's stream; on exit torch's stream waits for the ring's, so
-        # the blocks freed with them are reused only after the add read them
-        with self._torch_order():
-            check(self._lib.rb_add_particles_device(self._h, *[t.data_ptr() for t in ts], n, self._stream()),
-                  "rb_add_particles_device")
+        self._add_batch(feat, part, action, next_feat, next_part, reward, done)
 
     def add_batch_hindsight(self, feat, part, action, next_feat, next_part, reward, done, *, goal_cols, goals,
                             rewards):
@@ -609,135 +533,8 @@ class ReplayBuffer_particles(object):
         ``goals`` into columns ``goal_cols`` of feat and next_feat and ``rewards`` into the reward;
         the particle blocks, the action and done are the source transition's.  On CUDA tensors
         ``rb_add_particles_device_hindsight`` reads each source row once and stores it 1 + K times."""
-        self.flush()
-        if _is_cuda_tensor(feat):
-            ts, n = self._device_rows((feat, part, action, next_feat, next_part, reward, done),
-                                       "add_batch_hindsight: the seven inputs")
-            hs, keep = _hindsight_device(self.device, goal_cols, goals, rewards, n)
-            if n == 0:
-                return
-            if self._shadow is not None:
-                self._shadow.valid = False       # rows the host never saw: save() writes the ring
-            with self._torch_order():            # as _add_batch_device; `keep` lives until the exit
-                check(self._lib.rb_add_particles_device_hindsight(self._h, *[t.data_ptr() for t in ts], n, hs,
-                                                                  self._stream()),
-                      "rb_add_particles_device_hindsight")
-            return
-        F, npd, A = self.feat_dim, self._np(), self.action_dim
-        f = np.ascontiguousarray(feat, dtype=np.float64).reshape(-1, F)
-        n = f.shape[0]
-        arrs = [f] + [np.asarray(x, dtype=np.float64).reshape((-1, w) if w else (-1,))
-                      for x, w in ((part, npd), (action, A), (next_feat, F), (next_part, npd), (reward, 0),
-                                   (done, 0))]
-        if any(x.shape[0] != n for x in arrs):
-            raise ValueError("add_batch_hindsight: the seven inputs must have the same number of rows")
-        goals, rewards = np.asarray(goals), np.asarray(rewards)
-        cols, K, _ = _hindsight_dims(goal_cols, goals, rewards, n)
-        if n:
-            self.add_batch(*_hindsight_expand(arrs, (0, 3), 5, cols, K, goals, rewards))
-
-    def flush(self, stream=None):
-        _flush_stage(self, stream)
-
-    def fill_synthetic(self, n, max_action=1.0, seed=0):
-        self.flush()
-        if self._shadow is not None:
-            self._shadow.valid = False
-        check(self._lib.rb_fill_synthetic(self._h, int(n), float(max_action), int(seed), self._stream()),
-              "rb_fill_synthetic")
-
-    def sample(self, batch_size, indices=None, return_indices=False):
-        """my_replay_buffer.py:58-69: the 7 fp32 device tensors."""
-        torch = _torch()
-        self.flush()
-        B = int(batch_size)
-        dev = self.device
-        N, D, F, A = self.n_particles, self.particle_dim, self.feat_dim, self.action_dim
-        out = (torch.empty((B, F), device=dev), torch.empty((B, N, D), device=dev),
-               torch.empty((B, A), device=dev), torch.empty((B, F), device=dev),
-               torch.empty((B, N, D), device=dev), torch.empty((B, 1), device=dev),
-               torch.empty((B, 1), device=dev))
-        idx_out = torch.empty((B,), device=dev, dtype=torch.int64)
-        inj = None
-        if indices is not None:
-            inj = torch.as_tensor(np.asarray(indices, dtype=np.int64), device=dev)
-            if inj.numel() != B:
-                raise ValueError("indices must have batch_size entries")
-            size = self.size
-            if B and (int(inj.min()) < 0 or int(inj.max()) >= max(size, 1)):
-                raise IndexError("index out of range of the filled buffer")
-        with self._torch_order():
-            check(self._lib.rb_sample_particles(self._h, B, *[t.data_ptr() for t in out],
-                                                inj.data_ptr() if inj is not None else None,
-                                                idx_out.data_ptr(), self._stream()), "rb_sample_particles")
-        if return_indices:
-            return out, idx_out
-        return out
-
-    # ------------------------------------------------------------------ persistence
-    def _offsets(self):
-        F, npd, A = self.feat_dim, self._np(), self.action_dim
-        o = {}
-        c = 0
-        for name, w in (("state_features", F), ("state_particles", npd), ("action", A),
-                        ("next_state_features", F), ("next_state_particles", npd), ("reward", 1),
-                        ("not_done", 1)):
-            o[name] = (c, w)
-            c += w
-        return o
-
-    def _records(self):
-        n = self.max_size
-        rec = np.empty((n, self.record_floats), dtype=np.float32)
-        check(self._lib.rb_read_records(self._h, 0, n, _lib.fptr(rec)), "rb_read_records")
-        return rec
-
-    def save(self, folder):
-        """my_replay_buffer.py:24-32 (ptr / size pickled with protocol 4, arrays np.save'd; the
-        float64 host shadow when kept)."""
-        self.flush()
-        info = self._info()
-        sh = self._shadow
-        if sh is not None and sh.valid:
-            assert sh.ptr == int(info.ptr) % sh.cap, "host shadow out of step with the ring"
-            _save_folder(folder, info.ptr, info.size, sh.arrays)
-            return
-        n = self.max_size
-        rec = self._records()
-        shapes = self._shapes(n)
-        _save_folder(folder, info.ptr, info.size,
-                     {name: rec[:, c:c + w].astype(np.float64).reshape(shapes[name])
-                      for name, (c, w) in self._offsets().items()})
-
-    def load(self, folder):
-        """my_replay_buffer.py:34-44 (int-only unpickler for ptr / size)."""
-        self._n = 0                         # rows added before a load are replaced with it
-        ptr = _load_int(os.path.join(folder, "ptr.pkl"))
-        size = _load_int(os.path.join(folder, "size.pkl"))
-        arrs = {}
-        for attrib in self.store_np:
-            with open(os.path.join(folder, attrib + ".pkl"), "rb") as f:
-                arrs[attrib] = np.load(f, allow_pickle=False)
-        n = arrs["state_features"].shape[0]
-        self.feat_dim = arrs["state_features"].shape[1]
-        self.n_particles, self.particle_dim = arrs["state_particles"].shape[1:3]
-        self.action_dim = arrs["action"].shape[1]
-        self._create(n)
-        if self.host_shadow:
-            self._shadow = _HostShadow(arrs, ptr)
-        rec = np.zeros((n, self.record_floats), dtype=np.float32)
-        for name, (c, w) in self._offsets().items():
-            rec[:, c:c + w] = arrs[name].reshape(n, w)
-        check(self._lib.rb_write_records(self._h, 0, n, _lib.fptr(rec), ptr % n, min(size, n)),
-              "rb_write_records")
-
-    def __del__(self):
-        try:
-            if self._h is not None and _lib.alive():
-                self._lib.rb_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._add_batch_hindsight((feat, part, action, next_feat, next_part, reward, done), goal_cols, goals,
+                                  rewards)
 
 
 # The reference's module-level alias used by main.py:204-208.
