@@ -27,6 +27,9 @@
  *   rb_add_device_hindsight / rb_add_particles_device_hindsight
  *                        add_to_replay_buffer with --hindsight_number K on device rows: each
  *                        transition and its K relabels in one fan-out add      main.py:70-91
+ *   rb_add_device_nstep / rb_add_particles_device_nstep
+ *                        n-step returns on device rows (no counterpart in the reference): each tick's
+ *                        rows are stored and the previous n-1 ticks' rows mature in the ring, in one launch
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -151,6 +154,45 @@ int rb_add_device_hindsight(rb_handle* h, const float* state, const float* actio
 int rb_add_particles_device_hindsight(rb_handle* h, const float* feat, const float* part, const float* action,
                                       const float* next_feat, const float* next_part, const float* reward,
                                       const float* done, int64_t n, const rb_hindsight* hs, void* stream);
+/* N-step adds: rb_add_device / rb_add_particles_device for a vectorised rollout whose stored rows
+ * mature in the ring into multi-step transitions.  One call is one tick: `rows` environments, source
+ * row i always the same environment.  The tick's rows go to ring rows ptr, ptr+1, ... (wrapping) exactly
+ * as the plain device add stores them (not_done = 1.0f - done, a zeroed pad), and the same launch
+ * updates, for every environment whose episode is still running, the rows its previous up to n-1
+ * ticks stored: the row of j ticks ago gets reward += gpow[j] * reward[i] (fp32), this tick's
+ * next_state (particle rings: next_feat and next_particles) and not_done = gpow[j] * (1.0f - done[i]);
+ * its state, action (and feat / particles) columns keep their bits.  gpow[j] = (float) of the double
+ * product of j factors gamma, multiplied left to right; gpow[0] = 1.  A row stops maturing with the
+ * tick at which its environment has `ended` or done != 0, or after n ticks.
+ * Closed form: over the ticks 0..T-1 of one uninterrupted lane, with e the first tick >= t at which
+ * environment i has ended or done set (or infinity) and m = min(n, e - t + 1, T - t), the row of
+ * environment i's transition (s_t, a_t, r_t, s'_t, d_t) holds s_t, a_t, s'_{t+m-1},
+ * reward = sum_{k<m} gamma^k r_{t+k} and not_done = gpow[m-1] * (1 - d_{t+m-1}): at every moment an
+ * exact m-step transition for the learners' target y = r + (not_done * discount) * min Q', 1 <= m <= n,
+ * with no flush at episode ends and a fixed row count per tick.  The caller is responsible for gamma
+ * equalling the learner's discount.  rb_sample* and save() return the not_done column as stored, so it
+ * may be fractional.  n = 1 stores exactly what the plain device add stores.
+ * A lane is the run of consecutive n-step calls with the same rows, n and gamma; a call with another
+ * of these, and every other call that writes the ring (rb_add, rb_add_records, rb_add_device, both
+ * hindsight adds, the particle adds, rb_fill_synthetic, rb_write_records), ends it: the earlier rows stay
+ * as they are (a valid shorter horizon) and the next n-step call starts a fresh lane.
+ * Asynchronous on `stream`, ordered and with the pointer lifetimes of rb_add_device (`ended` included);
+ * `ns` itself is host memory read during the call only.  Checked in this order, each failure returning
+ * -1 with a message naming the field, before any GPU work and leaving ring, lane, ptr and size unchanged:
+ * rows >= 0; ns (non-null, n, gamma, ended); the handle; the ring kind (as rb_add_device /
+ * rb_add_particles_device); n * rows <= max_size (unlike the plain add, a tick is never truncated).
+ * rows == 0 then returns 0 and leaves the lane alone. */
+typedef struct rb_nstep {
+  int n;                  /* horizon, 1..8; 1 stores exactly what the plain device add stores */
+  double gamma;           /* the learner's discount, in (0, 1] */
+  const uint8_t* ended;   /* device [rows]: nonzero -> this row's episode ended with this transition,
+                             time limits included; a row with done != 0 counts as ended too */
+} rb_nstep;
+int rb_add_device_nstep(rb_handle* h, const float* state, const float* action, const float* next_state,
+                        const float* reward, const float* done, int64_t rows, const rb_nstep* ns, void* stream);
+int rb_add_particles_device_nstep(rb_handle* h, const float* feat, const float* part, const float* action,
+                                  const float* next_feat, const float* next_part, const float* reward,
+                                  const float* done, int64_t rows, const rb_nstep* ns, void* stream);
 /* The 7 tensors of ReplayBuffer_particles.sample (:58-69) into device outputs. */
 int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float* action, float* next_feat,
                         float* next_part, float* reward, float* not_done, const int64_t* inject_idx,

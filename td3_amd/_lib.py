@@ -50,6 +50,10 @@ class rb_hindsight(C.Structure):
                 ("rewards", C.c_void_p)]
 
 
+class rb_nstep(C.Structure):
+    _fields_ = [("n", C.c_int), ("gamma", C.c_double), ("ended", C.c_void_p)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -68,6 +72,9 @@ SIGNATURES = {
     "rb_add_device_hindsight": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(rb_hindsight), _P]),
     "rb_add_particles_device_hindsight": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64,
                                                     C.POINTER(rb_hindsight), _P]),
+    "rb_add_device_nstep": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(rb_nstep), _P]),
+    "rb_add_particles_device_nstep": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                                C.POINTER(rb_nstep), _P]),
     "rb_fill_synthetic": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     "rb_sample": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),

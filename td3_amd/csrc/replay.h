@@ -20,6 +20,7 @@ struct RingField {
   int off, len;                    // record columns [off, off + len)
 };
 constexpr int kRingFields = 7;
+constexpr int kMaxNstep = 8;       // longest n-step horizon (rb_nstep::n)
 
 struct Ring {
   uint64_t gen = 0;                // unique per allocation: captured graphs bake this ring in
@@ -58,6 +59,17 @@ struct Ring {
   hipEvent_t read_ev = nullptr, write_ev = nullptr;
   int64_t* d_idx = nullptr;        // last drawn indices (rows) of sample()
   int idx_cap = 0;
+  // The n-step lane (rb_add_device_nstep / rb_add_particles_device_nstep): the ring row of row 0 of
+  // the last ns_nhist n-step ticks, most recent first, and the (rows, n, gamma) they were stored with.
+  // Every other write of the ring ends the lane (ns_nhist = 0); the rows it leaves are valid
+  // shorter-horizon transitions.  ns_age[0] is read, ns_age[1] written by the next tick, then they swap.
+  int64_t ns_hist[kMaxNstep - 1] = {};
+  int ns_nhist = 0;
+  int64_t ns_rows = 0;
+  int ns_n = 0;
+  double ns_gamma = 0.0;
+  int* ns_age[2] = {nullptr, nullptr};   // device [ns_age_rows]: ticks of this environment's episode still maturing
+  int64_t ns_age_rows = 0;
 };
 
 // Reader protocol (Ring::read_stream): ring_begin_read before enqueuing reads on s (orders them

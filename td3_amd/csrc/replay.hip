@@ -11,6 +11,8 @@
 //                                               rb_add_particles_device (device rows)
 //   main.py add_to_replay_buffer    :70-91   -> rb_add_device_hindsight / rb_add_particles_device_hindsight
 //                                               (device rows, each stored with its K relabels)
+//   (none: n-step returns)                   -> rb_add_device_nstep / rb_add_particles_device_nstep
+//                                               (device rows of one tick; earlier ticks' rows mature in the ring)
 //
 // Both ring kinds are one ring whose record is a table of fields (replay.h Ring::field), filled with
 // the named offsets by ring_layout, the only place that computes an offset.  The host side of the two
@@ -379,6 +381,141 @@ __global__ __launch_bounds__(256) void ring_put_particles_hs_kernel(RingPutPartH
   if (blockIdx.x == 0 && tid == 0) *p.d_size = p.new_size;
 }
 
+// N-step adds (rb_add_device_nstep / rb_add_particles_device_nstep): one launch stores this tick's
+// one-step rows (copy 0, exactly the plain device add's records) and matures, in place, the rows the
+// previous ticks of the lane stored for the same environment: copy j = 1..a_i is ring row
+// hist[j - 1] + i (the row of source row i of the tick j ticks ago), whose reward gains
+// gpow[j] * reward[i], whose next-state block becomes this tick's and whose not_done becomes
+// gpow[j] * (1 - done[i]).  a_i = clamp(age_in[i], 0, nhist) is how many earlier ticks of environment
+// i's episode are still maturing; age_out[i] is that count for the next tick (0 once the episode ended).
+// age_in and age_out are different arrays (the host swaps them between ticks): every thread of a
+// source row reads age_in, one thread writes age_out.  The host keeps the row ranges of the 1 + nhist
+// ticks disjoint (n * rows <= cap), so each ring row belongs to one (i, j) and each of its 16-byte
+// units to one thread: the thread that stores the reward column is the one that read its old value.
+struct RingNstep {
+  const int* age_in;
+  int* age_out;
+  const uint8_t* ended;                     // [rows]
+  int64_t hist[kMaxNstep - 1];              // ring row of source row 0 of the tick j + 1 ticks ago, j < nhist
+  float gpow[kMaxNstep];                    // gamma^j
+  int nhist, nmax;                          // valid entries of hist; n - 1
+};
+__device__ __forceinline__ int nstep_age(const RingNstep& s, int64_t i) { return min(max(s.age_in[i], 0), s.nhist); }
+__device__ __forceinline__ void nstep_age_out(const RingNstep& s, int64_t i, int age, float done) {
+  s.age_out[i] = (s.ended[i] != 0 || done != 0.f) ? 0 : min(age + 1, s.nmax);
+}
+// Stores the four columns [c, c + 4) of a maturing row: one 16-byte store, or, in the unit that still
+// holds columns before the next-state block (o_s2 is in general no multiple of 4), dword stores of the
+// columns from o_s2 on -- the row's own action columns are not touched.
+__device__ __forceinline__ void nstep_store_unit(float* row, int c, int o_s2, const float (&w)[4]) {
+  if (c >= o_s2) {
+    *reinterpret_cast<float4*>(row + c) = make_float4(w[0], w[1], w[2], w[3]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (c + q >= o_s2) row[c + q] = w[q];
+  }
+}
+
+// The featured form: one thread per 16-byte unit of (source row, copy), as ring_put_device_kernel;
+// per source row the rec4 units of copy 0, then for each of the nhist possible earlier ticks the
+// units from the one holding column o_s2 on (u2 = o_s2 / 4).  A thread of a copy j > a_i has nothing
+// to do: the grid is sized by the host, which does not know the ages.
+struct RingPutDeviceNsArgs {
+  RingPutDeviceArgs p;                      // p.n source rows, p.skip = 0 (a tick is never truncated)
+  RingNstep s;
+  int u2, per_row;                          // per_row = rec4 + nhist * (rec4 - u2)
+};
+__global__ __launch_bounds__(256) void ring_put_device_ns_kernel(RingPutDeviceNsArgs a) {
+  const RingPutDeviceArgs& p = a.p;
+  const int mu = p.rec4 - a.u2;
+  const int64_t total = p.n * a.per_row;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / a.per_row;
+    int u = (int)(t - i * a.per_row);
+    const int age = nstep_age(a.s, i);
+    if (u < p.rec4) {                                          // copy 0: the plain add's record
+      const int c = u * 4;
+      int64_t dst = p.ptr + i;
+      if (dst >= p.cap) dst -= p.cap;
+      p.data[dst * p.rec4 + u] = make_float4(ring_put_device_elem(p, i, c), ring_put_device_elem(p, i, c + 1),
+                                             ring_put_device_elem(p, i, c + 2), ring_put_device_elem(p, i, c + 3));
+      if (u == 0) nstep_age_out(a.s, i, age, p.done[i]);
+      continue;
+    }
+    u -= p.rec4;
+    const int j = 1 + u / mu;
+    if (j > age) continue;
+    const int c = (a.u2 + (u - (j - 1) * mu)) * 4;
+    int64_t dst = a.s.hist[j - 1] + i;
+    if (dst >= p.cap) dst -= p.cap;
+    float* row = reinterpret_cast<float*>(p.data) + dst * (p.rec4 * 4);
+    const float g = a.s.gpow[j];
+    float w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int cc = c + q;
+      if (cc < p.o_s2) w[q] = 0.f;                             // not stored (nstep_store_unit)
+      else if (cc < p.o_r) w[q] = p.next_state[i * p.sd + (cc - p.o_s2)];
+      else if (cc == p.o_r) w[q] = row[cc] + g * p.reward[i];
+      else if (cc == p.o_nd) w[q] = g * (1.0f - p.done[i]);
+      else w[q] = 0.f;                                         // record pad
+    }
+    nstep_store_unit(row, c, p.o_s2, w);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *p.d_size = p.new_size;
+}
+
+// The particle form: one workgroup per (source row, tile) as ring_put_particles_hs_kernel -- the
+// tile's image is built in LDS once, so every source float is read once per tick, each thread takes
+// its float4 into registers and stores it to the new row and, where its unit reaches the next-state
+// blocks, to the a_i maturing rows.  The reward (old value + gpow[j] * this tick's), not_done and a
+// unit that straddles o_s2 are patched in a register copy; the LDS image is never patched.
+struct RingPutPartNsArgs {
+  RingPutPartArgs p;                        // p.n source rows, p.skip = 0
+  RingNstep s;
+  int o_s2, o_r;                            // next_feat, reward
+};
+__global__ __launch_bounds__(256) void ring_put_particles_ns_kernel(RingPutPartNsArgs a) {
+  __shared__ float4 img4[kPutTile / 4];
+  float* img = reinterpret_cast<float*>(img4);
+  const RingPutPartArgs& p = a.p;
+  const int tid = threadIdx.x;
+  const int64_t tiles = p.n * p.ntile;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t i = t / p.ntile;
+    const int c0 = (int)(t - i * p.ntile) * kPutTile, c1 = min(c0 + kPutTile, p.rec);
+    ring_put_build_tile(p, img, i, c0, c1, tid);
+    __syncthreads();
+    const int age = nstep_age(a.s, i);
+    const int c = c0 + 4 * tid;
+    if (c < c1) {
+      const float4 orig = img4[tid];
+      int64_t dst = p.ptr + i;
+      if (dst >= p.cap) dst -= p.cap;
+      p.data[(dst * p.rec + c) >> 2] = orig;
+      if (c + 4 > a.o_s2) {                                     // false for a whole tile below next_feat
+        for (int j = 1; j <= age; ++j) {
+          int64_t old = a.s.hist[j - 1] + i;
+          if (old >= p.cap) old -= p.cap;
+          float* row = reinterpret_cast<float*>(p.data) + old * p.rec;
+          const float g = a.s.gpow[j];
+          float w[4] = {orig.x, orig.y, orig.z, orig.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (c + q == a.o_r) w[q] = row[c + q] + g * w[q];
+            else if (c + q == p.o_nd) w[q] = g * w[q];          // the image holds 1 - done
+          }
+          nstep_store_unit(row, c, a.o_s2, w);
+        }
+      }
+    }
+    if (c0 == 0 && tid == 0) nstep_age_out(a.s, i, age, p.seg[kPutSegs - 1].src[i]);
+    __syncthreads();                                            // the image is reused by the next tile
+  }
+  if (blockIdx.x == 0 && tid == 0) *p.d_size = p.new_size;
+}
+
 // The lazy ordering of Ring::read_stream / write_stream: when `s` differs from the noted stream,
 // an event recorded there now (it covers everything queued so far) is waited on by `s`.
 static int order_after(hipStream_t s, hipStream_t noted, bool pending, hipEvent_t ev, hipStream_t& seen_by) {
@@ -451,10 +588,12 @@ static int64_t ring_reserve(Ring* r, int64_t rows, int64_t& skip, int64_t& new_s
   return rows;
 }
 
-// After the launches that wrote `rows` rows at r->ptr.
+// After the launches that wrote `rows` rows at r->ptr.  Any write ends the n-step lane: the rows that
+// follow are not the next tick of it (an n-step add sets its lane again after this).
 static int ring_wrote(Ring* r, int64_t rows, int64_t new_size, hipStream_t s) {
   r->ptr = (r->ptr + rows) % r->cap;
   r->size = new_size;
+  r->ns_nhist = 0;
   return ring_end_write(r, s);
 }
 
@@ -575,6 +714,7 @@ int rb_destroy(rb_handle* h) {
   (void)hipFree(r->data);
   (void)hipFree(r->d_size);
   (void)hipFree(r->d_idx);
+  for (int* age : r->ns_age) (void)hipFree(age);
   for (int i = 0; i < 2; ++i) {
     if (r->stage_buf_ev[i]) (void)hipEventSynchronize(r->stage_buf_ev[i]);
     if (r->stage[i]) (void)hipHostFree(r->stage[i]);
@@ -873,6 +1013,98 @@ int rb_add_particles_device_hindsight(rb_handle* h, const float* feat, const flo
   return device_add(r, ring_put_particles_hs_kernel, a, grid, a.p.n, a.p.new_size, stream);
 }
 
+// The checks of an rb_nstep that need no ring (made before the handle is looked at).
+static int nstep_check(const rb_nstep* ns) {
+  TD3_ARG(ns != nullptr, "null ns");
+  TD3_ARG(ns->n >= 1 && ns->n <= kMaxNstep, "ns->n must be in 1..8");
+  TD3_ARG(ns->gamma > 0.0 && ns->gamma <= 1.0, "ns->gamma must be in (0, 1]");
+  TD3_ARG(ns->ended != nullptr, "null ns->ended");
+  return 0;
+}
+
+// The lane a tick of `rows` rows continues (or starts: another rows / n / gamma than the lane's, or a
+// lane some other write ended) and the launch arguments that describe it.
+static int nstep_begin(Ring* r, int64_t rows, const rb_nstep* ns, RingNstep& s) {
+  if (r->ns_rows != rows || r->ns_n != ns->n || r->ns_gamma != ns->gamma) r->ns_nhist = 0;
+  if (r->ns_age_rows != rows) {
+    TD3_HIP(hipSetDevice(r->device));
+    for (int*& age : r->ns_age) {               // hipFree waits for the launches that still use them
+      (void)hipFree(age);
+      age = nullptr;
+    }
+    r->ns_age_rows = 0;
+    for (int*& age : r->ns_age) TD3_HIP(hipMalloc(&age, (size_t)rows * sizeof(int)));
+    r->ns_age_rows = rows;                      // contents unset: nhist = 0 clamps every age to 0
+  }
+  r->ns_rows = rows;
+  r->ns_n = ns->n;
+  r->ns_gamma = ns->gamma;
+  s = RingNstep{};
+  s.age_in = r->ns_age[0];
+  s.age_out = r->ns_age[1];
+  s.ended = ns->ended;
+  s.nhist = r->ns_nhist;
+  s.nmax = ns->n - 1;
+  for (int j = 0; j < s.nhist; ++j) s.hist[j] = r->ns_hist[j];
+  double g = 1.0;                               // gpow[j]: j factors of gamma multiplied left to right, in double
+  for (int j = 0; j < kMaxNstep; ++j, g *= ns->gamma) s.gpow[j] = (float)g;
+  return 0;
+}
+
+// After the launch of a tick that continued a lane of `nhist` ticks and stored its rows at `ptr`.
+static void nstep_end(Ring* r, int nhist, int64_t ptr) {
+  const int keep = std::min(nhist + 1, r->ns_n - 1);
+  for (int j = keep - 1; j > 0; --j) r->ns_hist[j] = r->ns_hist[j - 1];
+  if (keep > 0) r->ns_hist[0] = ptr;
+  r->ns_nhist = keep;
+  std::swap(r->ns_age[0], r->ns_age[1]);
+}
+
+int rb_add_device_nstep(rb_handle* h, const float* state, const float* action, const float* next_state,
+                        const float* reward, const float* done, int64_t rows, const rb_nstep* ns, void* stream) {
+  TD3_ARG(rows >= 0, "rows must be >= 0");
+  TD3_RC(nstep_check(ns));
+  TD3_ARG(h != nullptr, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(!r->particles, "rb_add_device_nstep on a particle ring (use rb_add_particles_device_nstep)");
+  TD3_ARG(rows <= r->cap / ns->n, "ns->n * rows must not exceed max_size (an n-step tick is never truncated)");
+  if (rows == 0) return 0;
+  TD3_ARG(state && action && next_state && reward && done, "null input");
+  RingPutDeviceNsArgs a{};
+  TD3_RC(nstep_begin(r, rows, ns, a.s));
+  a.p = ring_put_device_args(r, state, action, next_state, reward, done, rows);
+  a.u2 = r->o_s2 / 4;
+  a.per_row = a.p.rec4 + a.s.nhist * (a.p.rec4 - a.u2);
+  const int64_t ptr = r->ptr;
+  const int grid = (int)std::min<int64_t>((rows * a.per_row + 255) / 256, 1024);
+  TD3_RC(device_add(r, ring_put_device_ns_kernel, a, grid, rows, a.p.new_size, stream));
+  nstep_end(r, a.s.nhist, ptr);
+  return 0;
+}
+
+int rb_add_particles_device_nstep(rb_handle* h, const float* feat, const float* part, const float* action,
+                                  const float* next_feat, const float* next_part, const float* reward,
+                                  const float* done, int64_t rows, const rb_nstep* ns, void* stream) {
+  TD3_ARG(rows >= 0, "rows must be >= 0");
+  TD3_RC(nstep_check(ns));
+  TD3_ARG(h != nullptr, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(r->particles, "rb_add_particles_device_nstep on a featured ring (use rb_add_device_nstep)");
+  TD3_ARG(rows <= r->cap / ns->n, "ns->n * rows must not exceed max_size (an n-step tick is never truncated)");
+  if (rows == 0) return 0;
+  TD3_ARG(feat && part && action && next_feat && next_part && reward && done, "null input");
+  RingPutPartNsArgs a{};
+  TD3_RC(nstep_begin(r, rows, ns, a.s));
+  a.p = ring_put_part_args(r, {feat, part, action, next_feat, next_part, reward, done}, rows);
+  a.o_s2 = r->o_s2;
+  a.o_r = r->o_r;
+  const int64_t ptr = r->ptr;
+  const int grid = (int)std::min<int64_t>(rows * a.p.ntile, 4096);
+  TD3_RC(device_add(r, ring_put_particles_ns_kernel, a, grid, rows, a.p.new_size, stream));
+  nstep_end(r, a.s.nhist, ptr);
+  return 0;
+}
+
 int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, void* stream) {
   TD3_ARG(h != nullptr, "null handle");
   TD3_ARG(n >= 0, "n must be >= 0");
@@ -961,6 +1193,7 @@ int rb_write_records(rb_handle* h, int64_t start, int64_t n, const float* in, in
                     hipMemcpyHostToDevice));
   r->ptr = ptr;
   r->size = size;
+  r->ns_nhist = 0;                                   // the n-step lane ends with any other write
   TD3_HIP(hipMemcpy(r->d_size, &r->size, sizeof(int64_t), hipMemcpyHostToDevice));
   return 0;
 }

@@ -30,7 +30,9 @@ device memory, and no transition crosses the host (``tools/bench_rollout.py``). 
 and ring it is the same loop: ``rb_add_particles_device`` builds the wide records in the ring and the
 query's encoder reads the simulator's particle tensor in place.  With ``relabel=`` (hindsight,
 ``SyntheticGoalVecEnv``) each tick's transitions and their K relabels are stored by one fan-out add
-(``add_batch_hindsight``): the relabelled rows are never built outside the ring.
+(``add_batch_hindsight``): the relabelled rows are never built outside the ring.  With ``n_step=n``
+each tick is stored by ``add_batch_nstep``: the rows of the previous n - 1 ticks mature in the ring into
+multi-step transitions (include/td3.h), the train step unchanged.
 """
 from __future__ import annotations
 
@@ -344,11 +346,21 @@ class DeviceTrainLoop:
     ``relabel(env, state, action, reward, next_state, done_bool)``, when given, returns the tick's
     hindsight relabels ``(goal_cols, goals [n][K][G], rewards [n][K])`` (main.py:70-91; goals and
     rewards device tensors, made by the environment's own torch ops); the tick then stores each
-    transition and its K relabels through ``add_batch_hindsight``, still without a host copy."""
+    transition and its K relabels through ``add_batch_hindsight``, still without a host copy.
+
+    ``n_step`` > 1 stores each tick through ``add_batch_nstep(..., ended=done, n=n_step,
+    gamma=policy.discount)``: the rows of the previous ``n_step - 1`` ticks mature in the ring into
+    multi-step transitions, with no read-back of ``done``.  The stored ``done`` is still ``done_bool``,
+    so a time-limit end under ``done_swap`` bootstraps and stops maturing.  Not with ``relabel=``."""
 
     def __init__(self, env, policy, replay_buffer, *, start_policy, start_training, batch_size, expl_noise,
-                 done_swap=True, train_steps_per_tick=1, seed=0, relabel=None):
+                 done_swap=True, train_steps_per_tick=1, seed=0, relabel=None, n_step=1):
         from .exploration import DeviceOUNoise
+        self.n_step = int(n_step)
+        if self.n_step < 1:
+            raise ValueError(f"n_step must be >= 1, got {n_step}")
+        if self.n_step > 1 and relabel is not None:
+            raise ValueError("n_step > 1 cannot be combined with relabel= (n-step hindsight rows are not supported)")
         self.env, self.policy, self.replay_buffer = env, policy, replay_buffer
         self.start_policy, self.start_training = int(start_policy), int(start_training)
         self.batch_size = int(batch_size)
@@ -377,7 +389,9 @@ class DeviceTrainLoop:
             next_state, reward, done, time_limit = env.step(action)
             done_bool = (done & ~time_limit) if self.done_swap else done
             rows = (*state, action, *next_state) if isinstance(state, tuple) else (state, action, next_state)
-            if self.relabel is None:
+            if self.n_step > 1:
+                rb.add_batch_nstep(*rows, reward, done_bool, ended=done, n=self.n_step, gamma=policy.discount)
+            elif self.relabel is None:
                 rb.add_batch(*rows, reward, done_bool)
             else:
                 cols, goals, rewards = self.relabel(env, state, action, reward, next_state, done_bool)

@@ -328,6 +328,27 @@ class _RingBuffer(object):
         if n:
             self.add_batch(*_hindsight_expand(arrs, *self._relabel, cols, K, goals, rewards))
 
+    def _add_batch_nstep(self, arrays, ended, n, gamma):
+        self.flush()
+        if not all(_is_cuda_tensor(x) for x in (*arrays, ended)):
+            raise TypeError("add_batch_nstep takes CUDA tensors only: the stored rows mature in the ring "
+                            "on the device, there is no host path")
+        torch = _torch()
+        ts, rows = _device_rows(self.device, arrays, self._widths, f"add_batch_nstep: the {self._count} inputs")
+        if ended.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"add_batch_nstep: ended must be a bool or uint8 tensor, got {ended.dtype}")
+        e = ended.to(self.device).reshape(-1).contiguous().view(torch.uint8)
+        if e.shape[0] != rows:
+            raise ValueError(f"add_batch_nstep: ended must have one entry per row ({rows}), got {e.shape[0]}")
+        if rows == 0:                            # an empty tensor has no address; the checks still run
+            e = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        ns = _lib.rb_nstep()
+        ns.n, ns.gamma, ns.ended = int(n), float(gamma), e.data_ptr()
+        with self._torch_order():                # as _add_batch_device; `e` lives until the exit
+            self._call(self._C["add_device_nstep"], self._h, *[t.data_ptr() for t in ts], rows, ns, self._stream())
+        if rows and self._shadow is not None:
+            self._shadow.valid = False           # rows the host never saw: save() writes the ring
+
     def fill_synthetic(self, n, max_action=1.0, seed=0):
         """Device-side prefill with the SURVEY §8(d) synthetic distribution (bench/tests)."""
         self.flush()
@@ -416,7 +437,8 @@ class ReplayBuffer_featured(_RingBuffer):
 
     store_np = ["state", "action", "next_state", "reward", "not_done"]
     _C = {"create": "rb_create", "add": "rb_add", "add_device": "rb_add_device",
-          "add_device_hindsight": "rb_add_device_hindsight", "sample": "rb_sample"}
+          "add_device_hindsight": "rb_add_device_hindsight", "add_device_nstep": "rb_add_device_nstep",
+          "sample": "rb_sample"}
     _count = "five"
     _relabel = ((0, 2), 3)
     _stage_rows = _STAGE_ROWS
@@ -468,6 +490,18 @@ class ReplayBuffer_featured(_RingBuffer):
         no expanded copy is made); host arrays are expanded in float64 and take the host add."""
         self._add_batch_hindsight((state, action, next_state, reward, done), goal_cols, goals, rewards)
 
+    def add_batch_nstep(self, state, action, next_state, reward, done, *, ended, n, gamma):
+        """One tick of a vectorised device rollout with n-step returns (``rb_add_device_nstep``): row i is
+        environment i at every call.  The tick's rows are stored as ``add_batch`` stores them and, in
+        the same launch, the rows the previous ``n - 1`` ticks stored for an environment whose episode
+        still runs mature in place: reward ``+= gamma**j * reward[i]``, next_state becomes this
+        tick's, not_done ``gamma**j * (1 - done[i])``.  Every ring row is at every moment an exact
+        m-step transition (1 <= m <= n) for a learner whose ``discount`` is ``gamma``; ``sample``
+        returns the fractional not_done as stored.  ``ended`` (bool or uint8 ``[rows]``) marks the rows
+        whose episode ended with this transition, time limits included.  CUDA tensors only.  Any other
+        write of the ring, or another ``rows`` / ``n`` / ``gamma``, starts a fresh lane."""
+        self._add_batch_nstep((state, action, next_state, reward, done), ended, n, gamma)
+
 
 class ReplayBuffer_particles(_RingBuffer):
     """Particle-observation replay ring (my_replay_buffer.py:6-69) resident in HBM.
@@ -481,7 +515,8 @@ class ReplayBuffer_particles(_RingBuffer):
     store_np = ["state_features", "state_particles", "action", "next_state_features",
                 "next_state_particles", "reward", "not_done"]
     _C = {"create": "rb_create_particles", "add": "rb_add_particles", "add_device": "rb_add_particles_device",
-          "add_device_hindsight": "rb_add_particles_device_hindsight", "sample": "rb_sample_particles"}
+          "add_device_hindsight": "rb_add_particles_device_hindsight",
+          "add_device_nstep": "rb_add_particles_device_nstep", "sample": "rb_sample_particles"}
     _count = "seven"
     _relabel = ((0, 3), 5)
     _stage_rows = max(1, _STAGE_ROWS // 16)
@@ -535,6 +570,12 @@ class ReplayBuffer_particles(_RingBuffer):
         ``rb_add_particles_device_hindsight`` reads each source row once and stores it 1 + K times."""
         self._add_batch_hindsight((feat, part, action, next_feat, next_part, reward, done), goal_cols, goals,
                                   rewards)
+
+    def add_batch_nstep(self, feat, part, action, next_feat, next_part, reward, done, *, ended, n, gamma):
+        """``ReplayBuffer_featured.add_batch_nstep`` for particle transitions
+        (``rb_add_particles_device_nstep``): a maturing row receives this tick's next_feat and
+        next_particles; its feat, particles and action stay.  Each source row is read once per tick."""
+        self._add_batch_nstep((feat, part, action, next_feat, next_part, reward, done), ended, n, gamma)
 
 
 # The reference's module-level alias used by main.py:204-208.

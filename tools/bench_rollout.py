@@ -2,7 +2,7 @@
 """Env-steps/s of a rollout on a GPU-resident vector environment: host-vector path vs device path.
 
     python tools/bench_rollout.py [--config featured|particles] [--ticks K] [--warmup W] [--train-steps T]
-                                  [--hindsight K [--n-envs N] [--repeats R]] [--out FILE]
+                                  [--hindsight K | --nstep N [--n-envs E] [--repeats R]] [--out FILE]
 
 Both paths act on the same ``SyntheticVecEnv`` (HalfCheetah dims: 17 / 6, torch ops on device rows)
 with the same learner and replay ring, act -> env.step -> add per tick over ``n_envs`` rows:
@@ -38,6 +38,15 @@ One JSON line: for each form the add's effective GB/s (ring bytes written + sour
 numerator for both, over the device time of one call) and the env-steps/s of ``DeviceTrainLoop`` with a
 ``relabel`` (median of ``--repeats`` alternated runs), the two ratios, and the fan-out kernel's own time
 between two events on the ring's stream (the method of the plain add's ``device_add_gb_per_s``).
+
+``--nstep N`` (either config; ``--n-envs``, default 256) measures the n-step add
+(``rb_add_device_nstep`` / ``rb_add_particles_device_nstep``) instead.  One JSON line: the device time
+of one n-step add in steady state (no episode ends: every row matures its N - 1 predecessors) next to
+the plain device add's at the same shapes, both between two events on the ring's stream (median of 20
+after a warm-up); the algorithmic bytes written by each (the records, plus per maturing copy the
+next-state block and the two scalars) and the n-step add's time predicted from them at the plain add's
+achieved bytes per second; and the env-steps/s of ``DeviceTrainLoop`` with ``n_step=N`` against
+``n_step=1`` (median of ``--repeats`` alternated runs).
 """
 from __future__ import annotations
 
@@ -335,6 +344,107 @@ def hindsight_main(args, emit):
         "ticks": args.ticks, "warmup": args.warmup, "train_steps_per_tick": args.train_steps, "n_gpus": 1}))
 
 
+def nstep_add_us(env, rb, particles, n_step, reps=20):
+    """Device time (us) of one add of env.n_envs rows, event-timed as ``device_add_gbps`` /
+    ``fanout_kernel_gbps`` (two events on the ring's stream around the C call, median of `reps`, after
+    a warm-up): ``n_step`` 0 is the plain device add, otherwise the n-step add in steady state -- no
+    episode ends, so after n_step - 1 warm-up ticks every row matures its n_step - 1 predecessors."""
+    import torch
+    from td3_amd import _lib
+    n = env.n_envs
+    state = env.reset()
+    action = torch.zeros((n, env.action_space.shape[0]), device=env.device)
+    next_state, reward, done, _ = env.step(action)
+    rows = (*state, action, *next_state, reward, done) if particles else (state, action, next_state, reward, done)
+    ts = [t.to(torch.float32).reshape(n, -1).contiguous() for t in rows]
+    ts[-1].zero_()                                   # done = 0: nothing stops maturing
+    ended = torch.zeros(n, dtype=torch.uint8, device=env.device)
+    ns = _lib.rb_nstep()
+    ns.n, ns.gamma, ns.ended = max(n_step, 1), 0.99, ended.data_ptr()
+    kind = "particles_device" if particles else "device"
+    if n_step:
+        fn = getattr(rb._lib, f"rb_add_{kind}_nstep")
+        call = lambda: fn(rb.handle, *[t.data_ptr() for t in ts], n, ns, None)
+    else:
+        fn = getattr(rb._lib, f"rb_add_{kind}")
+        call = lambda: fn(rb.handle, *[t.data_ptr() for t in ts], n, None)
+    stream = torch.cuda.ExternalStream(int(rb._lib.rb_stream(rb.handle)), device=env.device)
+    torch.cuda.synchronize()
+    ms = []
+    warm = max(3, n_step)
+    for k in range(warm + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        rc = call()
+        e1.record(stream)
+        assert rc == 0, rb._lib.td3_last_error()
+        stream.synchronize()
+        if k >= warm:
+            ms.append(e0.elapsed_time(e1))
+    return 1e3 * float(np.median(ms))
+
+
+def nstep_main(args, emit):
+    """``--nstep N``: the n-step add next to the plain device add at the same shapes, and the loop."""
+    import torch
+    from td3_amd.loop import DeviceTrainLoop, SyntheticParticleVecEnv, SyntheticVecEnv
+    particles, N, n_envs = args.config == "particles", args.nstep, args.n_envs
+    if particles:
+        from td3_amd.TD3_particles import TD3
+        from td3_amd.my_replay_buffer import ReplayBuffer_particles as Ring
+        ring_rows, prefill, what = 100_000, 20_000, "SyntheticParticleVecEnv (7 / 350 x 9 / 3)"
+        make_env = lambda: SyntheticParticleVecEnv(n_envs, PF, PN, PD, PA, max_action=MA, max_episode_steps=1000)
+        next_block = PF + PN * PD
+    else:
+        from td3_amd.TD3_featured import TD3
+        from td3_amd.my_replay_buffer import ReplayBuffer_featured as Ring
+        ring_rows, prefill, what = 1_000_000, 100_000, "SyntheticVecEnv (HalfCheetah dims)"
+        make_env = lambda: SyntheticVecEnv(n_envs, SD, AD, max_action=MA, max_episode_steps=1000)
+        next_block = SD
+    np.random.seed(0)
+    torch.manual_seed(0)
+    env = make_env()
+    pol = TD3(env.observation_space, env.action_space, max_action=MA, norm="layer", device=env.device.index)
+    rings = {}
+    for form in ("nstep", "plain"):
+        rings[form] = Ring(env.observation_space, env.action_space, max_size=ring_rows, device=env.device.index)
+        rings[form].fill_synthetic(prefill, max_action=MA, seed=1)
+    rec = int(rings["nstep"].record_floats)
+    plain_us = nstep_add_us(env, rings["plain"], particles, 0)
+    nstep_us = nstep_add_us(env, rings["nstep"], particles, N)
+    # algorithmic bytes written: the new records, plus per maturing copy the next-state block and the two scalars
+    plain_bytes = 4 * n_envs * rec
+    nstep_bytes = plain_bytes + 4 * n_envs * (N - 1) * (next_block + 2)
+    predicted_us = plain_us * nstep_bytes / plain_bytes        # at the plain add's achieved bytes per second
+    sps = {form: [] for form in rings}
+    for rep in range(1 + args.repeats):              # the forms alternate; the first pass is the warm-up
+        for form, rb in rings.items():
+            loop = DeviceTrainLoop(env, pol, rb, start_policy=0, start_training=0, batch_size=args.batch,
+                                   expl_noise=0.1, train_steps_per_tick=args.train_steps,
+                                   n_step=N if form == "nstep" else 1)
+            r = loop.run(args.warmup if rep == 0 else args.ticks)
+            if rep:
+                sps[form].append(r["env_steps_per_s"])
+    ns_sps, one_sps = float(np.median(sps["nstep"])), float(np.median(sps["plain"]))
+    emit(json.dumps({
+        "metric": f"n-step add, n = {N}, on {what}: one add of {n_envs} rows in steady state (every row matures "
+                  f"its {N - 1} predecessors) next to the plain device add; act -> env.step -> add loop with "
+                  f"{args.train_steps} train({args.batch}) per tick, n_step = {N} against n_step = 1",
+        "n_envs": n_envs, "n_step": N, "record_floats": rec, "next_state_floats": next_block,
+        "plain_add_device_us": round(plain_us, 2), "nstep_add_device_us": round(nstep_us, 2),
+        "nstep_over_plain_time": round(nstep_us / plain_us, 3),
+        "plain_add_bytes_written": plain_bytes, "nstep_add_bytes_written": nstep_bytes,
+        "nstep_over_plain_bytes": round(nstep_bytes / plain_bytes, 3),
+        "nstep_add_us_at_plain_bandwidth": round(predicted_us, 2),
+        "nstep_measured_over_predicted": round(nstep_us / predicted_us, 3),
+        "nstep_steps_per_s": round(ns_sps, 1), "one_step_steps_per_s": round(one_sps, 1),
+        "steps_nstep_over_one_step": round(ns_sps / one_sps, 3),
+        "nstep_steps_per_s_runs": [round(x, 1) for x in sps["nstep"]],
+        "one_step_steps_per_s_runs": [round(x, 1) for x in sps["plain"]],
+        "unit": "us (add, lower is better), env-steps/s (loop, higher is better)",
+        "ticks": args.ticks, "warmup": args.warmup, "train_steps_per_tick": args.train_steps, "n_gpus": 1}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=("featured", "particles"), default="featured")
@@ -346,18 +456,25 @@ def main():
                     help="--config particles: one more line, the device add's GB/s for this many rows")
     ap.add_argument("--hindsight", type=int, default=0,
                     help="K > 0: compare the fan-out hindsight add with the torch expansion + add_batch instead")
-    ap.add_argument("--n-envs", type=int, default=256, help="--hindsight: environments (default 256)")
-    ap.add_argument("--repeats", type=int, default=3, help="--hindsight: timed loop runs per form (median)")
+    ap.add_argument("--nstep", type=int, default=0,
+                    help="N in 2..8: measure the n-step add against the plain device add, and the loop, instead")
+    ap.add_argument("--n-envs", type=int, default=256, help="--hindsight / --nstep: environments (default 256)")
+    ap.add_argument("--repeats", type=int, default=3,
+                    help="--hindsight / --nstep: timed loop runs per form (median)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
-    if args.hindsight > 0:
+    if args.hindsight > 0 or args.nstep > 0:
         def emit_line(line):
             print(line, flush=True)
             if args.out:
                 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
-        hindsight_main(args, emit_line)
+        if args.hindsight > 0 and args.nstep > 0:
+            ap.error("--hindsight and --nstep are separate measurements")
+        if args.nstep > 0 and not 2 <= args.nstep <= 8:
+            ap.error("--nstep takes a horizon in 2..8")
+        (hindsight_main if args.hindsight > 0 else nstep_main)(args, emit_line)
         return
     import torch
     from td3_amd.loop import SyntheticParticleVecEnv, SyntheticVecEnv
