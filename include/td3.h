@@ -30,6 +30,10 @@
  *   rb_add_device_nstep / rb_add_particles_device_nstep
  *                        n-step returns on device rows (no counterpart in the reference): each tick's
  *                        rows are stored and the previous n-1 ticks' rows mature in the ring, in one launch
+ *   rb_enable_priorities / rb_set_priorities / rb_update_priorities / rb_sample_prioritized /
+ *   td3_train_step_prioritized
+ *                        prioritized experience replay on the device ring (no counterpart in the
+ *                        reference): a 64-ary sum tree next to the ring, the weighted critic loss
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -198,8 +202,66 @@ int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float
                         float* next_part, float* reward, float* not_done, const int64_t* inject_idx,
                         int64_t* idx_out, void* stream);
 
+/* Prioritized replay (Schaul et al. 2016): optional per-row priorities of a ring of either kind, kept
+ * outside the records in a 64-ary sum tree (level 0: one fp32 leaf per row; each higher level one fp32
+ * per 64 nodes below, every level zero-padded to a multiple of 64, up to a single root group of 64;
+ * max_size = 10^6 gives 4 levels).  rb_info_t, the record layout, rb_read_records / rb_write_records and
+ * save() files do not change, and a ring without priorities queues not one extra launch or byte.
+ * At every stream-ordered point between calls: a leaf is > 0 exactly for the rows < size that hold a
+ * transition (unless rb_set_priorities stored a 0); every inner node is the sum of its 64 children as
+ * last recomputed; max_priority (a device scalar, 1.0f at first) is at least every priority stored so
+ * far; the total mass is the sum of the root group.  Sums are never updated by deltas or float atomics:
+ * a store writes the leaves and then, level by level, recomputes every affected parent from all 64 of
+ * its children in one fixed order, so duplicate indices are harmless and the tree is bit for bit
+ * reproducible.
+ * New rows: every call that writes the ring gives the rows it wrote max_priority, on the stream of the
+ * write -- rb_add, rb_add_records, rb_add_device, rb_add_particles(_device), both hindsight adds (all
+ * n*(1+k) rows), both n-step adds (the tick's new rows only: rows that mature in place keep their
+ * priority), rb_fill_synthetic; rb_write_records gives rows [0, size) max_priority and the rest 0.
+ * rb_enable_priorities: allocates the tree and gives rows [0, size) priority 1.0f, on `stream`, ordered
+ *   as a ring write.  Checked in this order: alpha in [0, 1]; eps > 0; the handle; not already enabled.
+ * rb_set_priorities: leaves idx[i] = p[i] as given (DEVICE arrays; finite and >= 0; neither alpha nor
+ *   eps is applied; 0 takes the row out of the draw), raises max_priority, repairs the parents.  A
+ *   row named several times in one call ends with the largest of its values, whatever the order.
+ * rb_update_priorities: the same with p = powf(td_abs[i] + eps, alpha) in fp32 (a non-finite result
+ *   stores the current max_priority instead).  Both are asynchronous on `stream`, ordered as a ring
+ *   write, and check in this order: n >= 0; non-null idx and values when n > 0; the handle; priorities
+ *   enabled.  n == 0 returns 0.  Indices are trusted to be < max_size, as rb_sample's inject_idx is.
+ * rb_sample_prioritized: `batch` rows drawn in proportion to their priorities into idx_out, their
+ *   importance weights into weight_out (DEVICE arrays [batch]); asynchronous on `stream`, ordered as a
+ *   ring read.  The draw is stratified: draw k has the mass fraction u_k = (k + U_k) / batch (fp32,
+ *   kept below 1), U_k in [0, 1) from Philox4x32-10 with the ring's seed as key and the counter
+ *   (k, stream id 5, step lo, step hi) -- a stream id of its own next to the learner's target noise (2)
+ *   and the exploration draw (4) -- where step is the ring's sample-call counter (shared with rb_sample,
+ *   advanced by every call); with inject_u (device [batch], nullable) u_k = inject_u[k] itself.  The mass
+ *   m = u_k * total is one fp32 multiply.  Descent, from the root group down: the first child whose
+ *   inclusive prefix sum (fp32, in the order the parents were summed) exceeds m, m less the prefix
+ *   before it; where rounding leaves none, the last child with a non-zero value.  A row of priority 0 is
+ *   never returned.  weight_out[k] = w_k / max_j w_j with w = (size * p / total)^(-beta) in fp32: the
+ *   weights are normalised by the maximum of the BATCH (as Dopamine does), not of the buffer, which
+ *   would need a min-tree for no practical gain.  Checked in this order: batch > 0; beta in [0, 1];
+ *   non-null outputs; the handle; priorities enabled; size > 0.
+ * rb_get_priorities: leaves [start, start + n) to the host; synchronous.
+ * rb_priority_info: synchronous; a ring without priorities reports enabled = 0 (and returns 0: this is
+ *   the query for it); every other call above returns -1 on such a ring.
+ * Every failure returns -1 before any GPU work, with a message naming the field. */
+typedef struct rb_priority_info_t {
+  int enabled;
+  double alpha, eps;
+  int levels;
+  double total;            /* the root sum, widened from the device's fp32 */
+  float max_priority;
+} rb_priority_info_t;
+int rb_enable_priorities(rb_handle* h, double alpha, double eps, void* stream);
+int rb_set_priorities(rb_handle* h, const int64_t* idx, const float* p, int64_t n, void* stream);
+int rb_update_priorities(rb_handle* h, const int64_t* idx, const float* td_abs, int64_t n, void* stream);
+int rb_sample_prioritized(rb_handle* h, int batch, double beta, const float* inject_u, int64_t* idx_out,
+                          float* weight_out, void* stream);
+int rb_get_priorities(const rb_handle* h, int64_t start, int64_t n, float* host_out);
+int rb_priority_info(const rb_handle* h, rb_priority_info_t* info);
+
 /* ------------------------------------------------------------------ learner */
-/* struct_size: sizeof(td3_config) as the caller compiled it.  td3_default_config sets it and
+/* struct_size:sizeof(td3_config) as the caller compiled it.  td3_default_config sets it and
  * td3_create refuses a config whose struct_size differs from the library's (a binding written
  * against another version of this header), before reading any other field. */
 typedef struct td3_config {
@@ -274,6 +336,27 @@ int td3_get_adam(const td3_handle* h, int group, double out[4] /* lr, beta1, bet
  * stats (nullable) forces a sync and fills losses. */
 int td3_train_step(td3_handle* h, rb_handle* rb, int batch, void* stream,
                    const int64_t* inject_idx, const float* inject_noise, td3_step_stats* stats);
+/* One TD3.train step on a prioritized draw (featured learners, one device).  On the step's stream,
+ * inside one read section of the ring (no add can overwrite a sampled row before its priority is
+ * written back): rb_sample_prioritized(batch, beta) straight into the step's index and weight buffers;
+ * the gather of those rows; the body of td3_train_step with the critic loss
+ * sum_j 1/B sum_r w_r (Q_j,r - y_r)^2, i.e. dL/dQ_j,r = 2/B w_r (Q_j,r - y_r) -- the actor loss is not
+ * weighted; rb_update_priorities(rows, td_abs) with td_abs_r = 0.5f * (|Q1_r - y_r| + |Q2_r - y_r|).
+ * No host synchronisation unless stats, per, inject_u or inject_noise force one.  inject_u [batch]
+ * (host, nullable) replaces the stratified Philox draw as in rb_sample_prioritized, inject_noise as in
+ * td3_train_step; stats->idx receives the rows drawn, stats->critic_loss the weighted loss; per
+ * (nullable) the weights and td_abs of the step.  Every other step entry point keeps unit weights: the
+ * first of them after a prioritized step refills the weight buffer on its own stream before its body.
+ * Returns -1 with a message for: a particle learner; a handle in a td3_comm_init or
+ * td3_comm_init_local group; a ring without priorities; a ring whose kind or dims do not match; beta
+ * outside [0, 1]; an empty ring. */
+typedef struct td3_per_stats {
+  float* weight;           /* nullable host [B]: importance weights used */
+  float* td_abs;           /* nullable host [B]: the |TD error| written back */
+} td3_per_stats;
+int td3_train_step_prioritized(td3_handle* h, rb_handle* rb, int batch, double beta, void* stream,
+                               const float* inject_u, const float* inject_noise, td3_step_stats* stats,
+                               td3_per_stats* per);
 /* Same step on an already-sampled batch (device float32 pointers, contiguous). */
 int td3_train_step_batch(td3_handle* h, const float* state, const float* action,
                          const float* next_state, const float* reward, const float* not_done,

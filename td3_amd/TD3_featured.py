@@ -224,6 +224,9 @@ class TD3(TD3_base):
         cfg.device = self._dev
         cfg.use_graph = 2 if use_graph == "auto" else (1 if use_graph else 0)
         self._cfg = cfg
+        # importance-weight exponent of the steps on a prioritized ring (enable_priorities); the user
+        # anneals it towards 1 (Schaul et al. 2016)
+        self.per_beta = 0.4
         h = C.c_void_p()
         check(self._lib.td3_create(C.byref(cfg), C.byref(h)), "td3_create")
         self._h = h
@@ -415,8 +418,12 @@ class TD3(TD3_base):
     def train(self, replay_buffer, batch_size=100):
         self.train_step(replay_buffer, batch_size)
 
-    def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False):
-        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back."""
+    def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False, u=None):
+        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back.  On a
+        prioritized ring (``enable_priorities``) without ``indices`` the step draws its rows by
+        priority, weights the critic loss with ``per_beta`` and writes the new priorities back, all on
+        the device; ``u`` (``[batch_size]`` mass fractions) replaces that draw and the stats gain
+        ``"weight"`` and ``"td_abs"``."""
         B = int(batch_size)
         st = None
         keep = []
@@ -433,7 +440,26 @@ class TD3(TD3_base):
         nz = None
         if noise is not None:
             nz = np.ascontiguousarray(np.asarray(noise, dtype=np.float32).reshape(B, self.action_dim))
-        if isinstance(replay_buffer, ReplayBuffer_featured):
+        prioritized = indices is None and getattr(replay_buffer, "prioritized", False)
+        if u is not None and not prioritized:
+            raise ValueError("u is the draw of a prioritized step: enable_priorities on the ring, no indices")
+        if prioritized and isinstance(replay_buffer, ReplayBuffer_featured):
+            replay_buffer.flush(self._lib.td3_stream(self._h))   # in the step's stream order
+            per = None
+            if stats:
+                per = _lib.td3_per_stats()
+                weight, td_abs = np.empty(B, np.float32), np.empty(B, np.float32)
+                per.weight, per.td_abs = weight.ctypes.data, td_abs.ctypes.data
+            uu = None
+            if u is not None:
+                uu = np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(B))
+            check(self._lib.td3_train_step_prioritized(self._h, replay_buffer.handle, B, float(self.per_beta),
+                                                       self._stream(), _lib.fptr(uu) if uu is not None else None,
+                                                       _lib.fptr(nz) if nz is not None else None,
+                                                       C.byref(st) if st is not None else None,
+                                                       C.byref(per) if per is not None else None),
+                  "td3_train_step_prioritized")
+        elif isinstance(replay_buffer, ReplayBuffer_featured):
             replay_buffer.flush(self._lib.td3_stream(self._h))   # in the step's stream order
             ix = None
             if indices is not None:
@@ -464,6 +490,8 @@ class TD3(TD3_base):
                "y": keep[0], "q1": keep[1], "q2": keep[2], "idx": keep[3], "noise": keep[4]}
         if st.actor_step:
             out["actor_loss"] = st.actor_loss
+        if prioritized:
+            out["weight"], out["td_abs"] = weight, td_abs
         return out
 
     def sync(self):

@@ -244,6 +244,10 @@ class TD3(_FeaturedTD3):
 
     def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False):
         """``train`` with optional injected sample indices / N(0,1) noise and loss read-back."""
+        if getattr(replay_buffer, "prioritized", False):
+            raise NotImplementedError("TD3_particles.TD3.train on a prioritized ring: the particle learner's "
+                                      "critic loss takes no importance weights (prioritized steps are "
+                                      "TD3_featured only); train on a ring without enable_priorities")
         B, A = int(batch_size), self.action_dim
         st = None
         keep = []

@@ -54,6 +54,15 @@ class rb_nstep(C.Structure):
     _fields_ = [("n", C.c_int), ("gamma", C.c_double), ("ended", C.c_void_p)]
 
 
+class rb_priority_info_t(C.Structure):
+    _fields_ = [("enabled", C.c_int), ("alpha", C.c_double), ("eps", C.c_double), ("levels", C.c_int),
+                ("total", C.c_double), ("max_priority", C.c_float)]
+
+
+class td3_per_stats(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("td_abs", C.c_void_p)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -77,6 +86,12 @@ SIGNATURES = {
                                                 C.POINTER(rb_nstep), _P]),
     "rb_fill_synthetic": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     "rb_sample": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rb_enable_priorities": (C.c_int, [_P, C.c_double, C.c_double, _P]),
+    "rb_set_priorities": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "rb_update_priorities": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "rb_sample_prioritized": (C.c_int, [_P, C.c_int, C.c_double, _P, _P, _P, _P]),
+    "rb_get_priorities": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
+    "rb_priority_info": (C.c_int, [_P, C.POINTER(rb_priority_info_t)]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
     "rb_write_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F, C.c_int64, C.c_int64]),
     "rb_sync": (C.c_int, [_P]),
@@ -98,6 +113,8 @@ SIGNATURES = {
     "td3_set_adam": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
     "td3_get_adam": (C.c_int, [_P, C.c_int, _D]),
     "td3_train_step": (C.c_int, [_P, _P, C.c_int, _P, _I64, _F, C.POINTER(td3_step_stats)]),
+    "td3_train_step_prioritized": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, _F, _F,
+                                             C.POINTER(td3_step_stats), C.POINTER(td3_per_stats)]),
     "td3_train_step_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _F,
                                        C.POINTER(td3_step_stats)]),
     "td3_select_action": (C.c_int, [_P, _F, _F, C.c_int]),

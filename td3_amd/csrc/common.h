@@ -78,7 +78,11 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 ctr, uint32_t k0, uint32_t 
 //   kStreamFill     the record column of rb_fill_synthetic (step = the row filled)
 //   kStreamExplore  row * ceil(action_dim / 4) + column / 4 of td3_select_action_device's
 //                   exploration draw (step = td3_explore::step, seed = td3_explore::seed)
-enum : uint32_t { kStreamIndex = 1u, kStreamNoise = 2u, kStreamFill = 3u, kStreamExplore = 4u };
+//   kStreamPriority draw k of rb_sample_prioritized / td3_train_step_prioritized: its place U_k in
+//                   stratum k (step = the ring's sample-call counter, seed = the ring's)
+enum : uint32_t {
+  kStreamIndex = 1u, kStreamNoise = 2u, kStreamFill = 3u, kStreamExplore = 4u, kStreamPriority = 5u
+};
 
 // Uniform integer in [0, n) from 64 random bits (multiply-high; bias < n / 2^64).
 __device__ __forceinline__ uint64_t philox_index(uint64_t seed, uint64_t step, uint32_t row,

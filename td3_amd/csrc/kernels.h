@@ -278,8 +278,10 @@ enum : int {
   kY = 14,       // out: target y [Bp]
   kDZ4,          // x2, out: dZ4 of Q_j (ld 32)
   kSqErr = 17,   // out: squared errors [2][Bp]
-  kG,            // x2, out: g_j = 2/B (Q_j - y) [Bp]
-  kNumPtr = 20
+  kG,            // x2, out: g_j = 2/B w (Q_j - y) [Bp]
+  kW = 20,       // importance weight of the row [Bp] (ones unless the step is prioritized)
+  kTd,           // out: 0.5 (|Q1 - y| + |Q2 - y|) of a live row, 0 for a pad row [Bp]
+  kNumPtr
 };
 enum : int {
   kK3 = 0,

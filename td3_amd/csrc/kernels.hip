@@ -1047,8 +1047,10 @@ __device__ __forceinline__ void row_unit_loss(const GemmProb& P, const RowCtx& c
 
 // ---- clipped double-Q target and the rows' loss gradients (kRowTargetLoss) -----------------
 // y = r + not_done * discount * min(Q1'(s',a'), Q2'(s',a')) (TD3_featured.py:140-142) and for both
-// online critics g_j = 2/B (Q_j - y) (F.mse_loss backward, :148): the head's dZ4_j and the row
-// scale of Q_j's unit backward in the dW stage; the squared errors for the loss read-back.
+// online critics g_j = 2/B w (Q_j - y) (F.mse_loss backward, :148, times the row's importance weight
+// w: 1 unless the step is prioritized, and then exact): the head's dZ4_j and the row scale of Q_j's
+// unit backward in the dW stage; the weighted squared errors for the loss read-back; the row's
+// |TD error|, the mean over the twin, for the priority write-back.
 // (operands: target_loss, kernels.h)
 template <bool NORM>
 __device__ __forceinline__ void row_target_loss(const GemmProb& P, const RowCtx& c) {
@@ -1058,7 +1060,8 @@ __device__ __forceinline__ void row_target_loss(const GemmProb& P, const RowCtx&
                "s"(P.ex[kReward]), "s"(P.ex[kNotDone]), "s"(P.ex[kQ]), "s"(P.ex[kQ + 1]), "s"(P.exi[kK3]),
                "s"(P.exi[kLd3]));
   asm volatile("" ::"s"(P.ex[kY]), "s"(P.ex[kDZ4]), "s"(P.ex[kDZ4 + 1]), "s"(P.ex[kSqErr]), "s"(P.ex[kG]),
-               "s"(P.ex[kG + 1]), "s"(P.exf[kDiscount]), "s"(P.exf[kGradScale]), "s"(P.B));
+               "s"(P.ex[kG + 1]), "s"(P.ex[kW]), "s"(P.ex[kTd]), "s"(P.exf[kDiscount]), "s"(P.exf[kGradScale]),
+               "s"(P.B));
   const int K3 = P.exi[kK3], ld3 = P.exi[kLd3];
   float x0[1][8], x1[1][8], g[2][8], bb[2][8], w[2][8];
   rv_load(x0[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
@@ -1074,6 +1077,7 @@ __device__ __forceinline__ void row_target_loss(const GemmProb& P, const RowCtx&
   const float b40 = gld(P.ex[kB4]), b41 = gld(P.ex[kB4 + 1]);
   const float rw = gld(P.ex[kReward] + c.row), nd = gld(P.ex[kNotDone] + c.row);
   const float q1 = gld(P.ex[kQ] + c.row), q2 = gld(P.ex[kQ + 1] + c.row);
+  const float iw = gld(P.ex[kW] + c.row);
   __builtin_amdgcn_sched_barrier(0);     // every load requested before the first use
   float m0[1], s0[1], m1[1], s1[1];
   if (NORM) {
@@ -1087,15 +1091,17 @@ __device__ __forceinline__ void row_target_loss(const GemmProb& P, const RowCtx&
   const bool live = c.row < P.B;
   const float e1 = q1 - y, e2 = q2 - y;
   // mse_loss bwd (:148)
-  const float g1 = live ? P.exf[kGradScale] * e1 : 0.f, g2 = live ? P.exf[kGradScale] * e2 : 0.f;
+  const float gs = P.exf[kGradScale] * iw;
+  const float g1 = live ? gs * e1 : 0.f, g2 = live ? gs * e2 : 0.f;
   if (c.lane == 0) {
     gst(P.ex[kY] + c.row, y);
     gst(P.ex[kDZ4] + ((size_t)c.row * 32), g1);
     gst(P.ex[kDZ4 + 1] + ((size_t)c.row * 32), g2);
-    gst(P.ex[kSqErr] + c.row, live ? e1 * e1 : 0.f);
-    gst(P.ex[kSqErr] + (c.Bp + c.row), live ? e2 * e2 : 0.f);
+    gst(P.ex[kSqErr] + c.row, live ? iw * e1 * e1 : 0.f);
+    gst(P.ex[kSqErr] + (c.Bp + c.row), live ? iw * e2 * e2 : 0.f);
     gst(P.ex[kG] + c.row, g1);
     gst(P.ex[kG + 1] + c.row, g2);
+    gst(P.ex[kTd] + c.row, live ? 0.5f * (fabsf(e1) + fabsf(e2)) : 0.f);
   }
 }
 

@@ -22,6 +22,24 @@ struct RingField {
 constexpr int kRingFields = 7;
 constexpr int kMaxNstep = 8;       // longest n-step horizon (rb_nstep::n)
 
+// Optional per-row priorities (rb_enable_priorities): a 64-ary sum tree outside the records.  Level 0
+// is one fp32 leaf per ring row, level l + 1 one fp32 per 64 nodes of level l; every level is padded
+// with zeros to a multiple of 64, and the top level is a single group of 64 (the root group).  The
+// radix is the wave width: the children of a node are one 256-byte load, and one wave finds the
+// child that holds a mass with a scan across its lanes.  A node is the scan sum (pri_group_sum,
+// replay.hip) of its 64 children as last recomputed -- never a running total of deltas; the total
+// mass is the same sum over the root group, which every draw loads as its first step anyway.
+constexpr int kMaxPriLevels = 8;   // 64^8 rows
+struct PriTree {
+  bool on = false;
+  double alpha = 0.0, eps = 0.0;
+  int levels = 0;
+  float* base = nullptr;                 // the levels one behind the other
+  float* level[kMaxPriLevels] = {};      // level[l]: len[l] floats (a multiple of 64)
+  int64_t len[kMaxPriLevels] = {};
+  float* d_max = nullptr;                // device scalar max_priority (raised by atomicMax on its bits)
+};
+
 struct Ring {
   uint64_t gen = 0;                // unique per allocation: captured graphs bake this ring in
   int sd = 0, ad = 0;
@@ -70,6 +88,7 @@ struct Ring {
   double ns_gamma = 0.0;
   int* ns_age[2] = {nullptr, nullptr};   // device [ns_age_rows]: ticks of this environment's episode still maturing
   int64_t ns_age_rows = 0;
+  PriTree pri;
 };
 
 // Reader protocol (Ring::read_stream): ring_begin_read before enqueuing reads on s (orders them
@@ -106,6 +125,16 @@ struct GatherArgs {
 };
 
 int launch_gather(const GatherArgs& a, hipStream_t s);
+
+// The prioritized draw of `batch` rows on `s` (rb_sample_prioritized, include/td3.h): the rows into
+// idx_out and idx_out2 (nullable), the importance weights, normalised by the batch maximum, into
+// weight_out.  inject_u: device, nullable.  The caller holds the ring's read section and has checked
+// that priorities are on and the ring is not empty.
+int ring_draw_prioritized(Ring* r, int batch, double beta, const float* inject_u, int64_t* idx_out,
+                          int64_t* idx_out2, float* weight_out, hipStream_t s);
+// Leaves idx[0..n) = p (td = false) or (p + eps)^alpha (td = true), max_priority raised, parents
+// repaired, on `s` (device arrays).  No stream ordering of its own: the caller's section provides it.
+int ring_store_priorities(Ring* r, const int64_t* idx, const float* p, int64_t n, bool td, hipStream_t s);
 
 // The ring-side members of a gather from `r` (the caller adds the segments, the batch and the draw).
 inline GatherArgs gather_base(const Ring* r) {

@@ -13,6 +13,9 @@
 //                                               (device rows, each stored with its K relabels)
 //   (none: n-step returns)                   -> rb_add_device_nstep / rb_add_particles_device_nstep
 //                                               (device rows of one tick; earlier ticks' rows mature in the ring)
+//   (none: prioritized replay)               -> rb_enable_priorities / rb_set_priorities / rb_update_priorities /
+//                                               rb_sample_prioritized (a 64-ary sum tree next to the ring; every
+//                                               write of the ring gives its rows max_priority, ring_wrote)
 //
 // Both ring kinds are one ring whose record is a table of fields (replay.h Ring::field), filled with
 // the named offsets by ring_layout, the only place that computes an offset.  The host side of the two
@@ -516,6 +519,168 @@ __global__ __launch_bounds__(256) void ring_put_particles_ns_kernel(RingPutPartN
   if (blockIdx.x == 0 && tid == 0) *p.d_size = p.new_size;
 }
 
+// ------------------------------------------------------------------ priorities
+// The 64-ary sum tree of replay.h PriTree.  Every kernel below gives one wave one group of 64
+// siblings: a coalesced 256-byte load, an inclusive scan across the lanes.  A parent is stored as
+// lane 63 of that scan, so the prefix sums a draw sees while it descends through a group end exactly
+// at the value its parent holds.  Updates store the changed leaves and then recompute, level by
+// level, every affected parent from all of its children: idempotent (duplicate indices store the same
+// value twice), free of float atomics and therefore bitwise reproducible whatever the arrival order.
+// A level is made visible to the next one by the launch boundary between them (one launch per level):
+// a stored node is another workgroup's input one level up, and inside a launch that hand-off would
+// need a release / acquire flag protocol across workgroups for a few microseconds of launch gaps.
+__device__ __forceinline__ float pri_group_scan(float v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// Leaves [start, start + n) (wrapping at cap) = max_priority: the rows an add just wrote.
+__global__ __launch_bounds__(256) void pri_fill_range_kernel(float* __restrict__ leaf, int64_t start, int64_t n,
+                                                             int64_t cap, const float* __restrict__ d_max) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  int64_t row = start + i;
+  if (row >= cap) row -= cap;
+  leaf[row] = *d_max;
+}
+
+// Leaves [0, size) = max_priority, [size, len) = 0: enable, rb_write_records.
+__global__ __launch_bounds__(256) void pri_reset_kernel(float* __restrict__ leaf, int64_t size, int64_t len,
+                                                        const float* __restrict__ d_max) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < len) leaf[i] = i < size ? *d_max : 0.f;
+}
+
+// Parents [p0a, p0a + na) and [p0b, p0b + nb) of one level from their children, one wave each.
+__global__ __launch_bounds__(256) void pri_repair_range_kernel(const float* __restrict__ child,
+                                                               float* __restrict__ parent, int64_t p0a, int64_t na,
+                                                               int64_t p0b, int64_t nb) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= na + nb) return;
+  const int64_t p = w < na ? p0a + w : p0b + (w - na);
+  const float s = pri_group_scan(child[p * 64 + lane], lane);
+  if (lane == 63) parent[p] = s;
+}
+
+// The parents idx[k] >> shift of one level, one wave per k (duplicates recompute the same value).
+__global__ __launch_bounds__(256) void pri_repair_idx_kernel(const float* __restrict__ child,
+                                                             float* __restrict__ parent,
+                                                             const int64_t* __restrict__ idx, int64_t n, int shift) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= n) return;
+  const int64_t p = idx[w] >> shift;
+  const float s = pri_group_scan(child[p * 64 + lane], lane);
+  if (lane == 63) parent[p] = s;
+}
+
+// Leaves idx[k] = p[k] (td = 0) or (p[k] + eps)^alpha (td = 1), in two launches: the leaves are
+// cleared, then every entry raises its leaf by an integer atomicMax on the float's bits (priorities
+// are non-negative: their bits order as they do).  A row that appears several times in one call
+// (a batch can draw a row twice, with different target noise and so different TD errors) ends with
+// the largest of its values whatever the order of arrival -- a plain store would keep whichever
+// landed last.  max_priority is raised the same way, once per wave.  A non-finite |TD error| (a
+// diverged critic) stores the current max_priority instead of poisoning every sum above the leaf.
+__global__ __launch_bounds__(256) void pri_clear_kernel(float* __restrict__ leaf, const int64_t* __restrict__ idx,
+                                                        int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) leaf[idx[i]] = 0.f;
+}
+__global__ __launch_bounds__(256) void pri_store_kernel(float* __restrict__ leaf, const int64_t* __restrict__ idx,
+                                                        const float* __restrict__ p, int64_t n, int td, float alpha,
+                                                        float eps, float* __restrict__ d_max) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float v = 0.f;
+  if (i < n) {
+    v = p[i];
+    if (td) {
+      v = powf(v + eps, alpha);
+      if (!(v >= 0.f && v <= 3.0e38f)) v = *d_max;
+    }
+    v = v > 0.f ? v : 0.f;                                      // (-0.0f and NaN have large bits)
+    atomicMax(reinterpret_cast<unsigned int*>(leaf + idx[i]), __float_as_uint(v));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0 && v > 0.f) atomicMax(reinterpret_cast<unsigned int*>(d_max), __float_as_uint(v));
+}
+
+// The stratified draw (rb_sample_prioritized), one wave per draw k: the mass m = u_k * total, with
+// u_k = (k + U_k) / batch (U_k in [0, 1) from Philox) or inject_u[k], then down the tree -- at each
+// level the first child whose inclusive prefix exceeds m, m less the prefix before it; where rounding
+// leaves none, the last child with a non-zero value.  A child chosen by its prefix has a value > 0
+// (its prefix exceeds its left neighbour's), so a row of priority 0 is never returned while any
+// priority is positive.  The raw weight (size * p / total)^-beta goes to w_raw; pri_normalise_kernel
+// divides the batch by its maximum.
+struct PriDrawArgs {
+  const float* level[kMaxPriLevels];
+  int levels, batch;
+  int64_t cap, size;
+  float beta;
+  const float* inject_u;
+  int64_t *idx_out, *idx_out2;
+  float* w_raw;
+  uint64_t seed, step;
+};
+__global__ __launch_bounds__(256) void pri_draw_kernel(PriDrawArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= a.batch) return;
+  float u;
+  if (a.inject_u) {
+    u = a.inject_u[k];
+  } else {
+    const u32x4 r = philox4x32_10(u32x4{(uint32_t)k, kStreamPriority, (uint32_t)a.step, (uint32_t)(a.step >> 32)},
+                                  (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const float U = (float)(r.x >> 8) * (1.0f / 16777216.0f);                  // [0, 1)
+    u = fminf(((float)k + U) / (float)a.batch, 0x1.fffffep-1f);                // (k + U) may round up to k + 1
+  }
+  float v = a.level[a.levels - 1][lane];
+  float s = pri_group_scan(v, lane);
+  const float total = __shfl(s, 63, 64);
+  float m = u * total;
+  int64_t node = 0;
+  for (int l = a.levels - 1;; --l) {
+    const unsigned long long over = __ballot(s > m), nz = __ballot(v > 0.f);
+    int c = 0;
+    if (over) c = __ffsll(over) - 1;
+    else if (nz) c = 63 - __clzll(nz);
+    const float before = __shfl(s, max(c - 1, 0), 64);
+    if (c > 0) m -= before;
+    node = node * 64 + c;
+    if (l == 0) {
+      v = __shfl(v, c, 64);
+      break;
+    }
+    v = a.level[l - 1][node * 64 + lane];
+    s = pri_group_scan(v, lane);
+  }
+  if (lane == 0) {
+    node = min(node, a.cap - 1);                               // (all priorities zero: any row, in bounds)
+    a.idx_out[k] = node;
+    if (a.idx_out2) a.idx_out2[k] = node;
+    a.w_raw[k] = powf((float)a.size * v / total, -a.beta);
+  }
+}
+
+// w[k] = w_raw[k] / max_j w_raw[j]: one workgroup (a batch is a few hundred rows).
+__global__ __launch_bounds__(256) void pri_normalise_kernel(const float* w_raw, float* w, int batch) {   // may alias
+  __shared__ float wmax[4];
+  float mx = 0.f;
+  for (int i = threadIdx.x; i < batch; i += 256) mx = fmaxf(mx, w_raw[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  for (int i = threadIdx.x; i < batch; i += 256) w[i] = w_raw[i] / mx;
+}
+
 // The lazy ordering of Ring::read_stream / write_stream: when `s` differs from the noted stream,
 // an event recorded there now (it covers everything queued so far) is waited on by `s`.
 static int order_after(hipStream_t s, hipStream_t noted, bool pending, hipEvent_t ev, hipStream_t& seen_by) {
@@ -588,9 +753,77 @@ static int64_t ring_reserve(Ring* r, int64_t rows, int64_t& skip, int64_t& new_s
   return rows;
 }
 
+// Recompute, level by level (one launch each), the parents above leaves [start, start + n), wrapping
+// at cap: per level the affected parents are one range, or two when the rows wrap.
+static int pri_repair_ranges(const PriTree& t, int64_t start, int64_t n, int64_t cap, hipStream_t s) {
+  const int64_t na0 = std::min(n, cap - start), nb0 = n - na0;     // leaves [start, start + na0) and [0, nb0)
+  for (int l = 1; l < t.levels; ++l) {
+    const int sh = 6 * l;
+    const int64_t a0 = start >> sh, a1 = (start + na0 - 1) >> sh;
+    int64_t b0 = 0, nb = nb0 > 0 ? ((nb0 - 1) >> sh) + 1 : 0;
+    if (nb > a0) nb = a0;                                          // the two ranges meet: [0, a1] once
+    const int64_t na = a1 - a0 + 1;
+    hipLaunchKernelGGL(pri_repair_range_kernel, dim3((unsigned)((na + nb + 3) / 4)), dim3(256), 0, s,
+                       t.level[l - 1], t.level[l], a0, na, b0, nb);
+  }
+  TD3_HIP(hipGetLastError());
+  return 0;
+}
+
+// The rows an add just wrote get max_priority (a new transition is drawn at least once soon).
+static int pri_wrote(Ring* r, int64_t start, int64_t rows, hipStream_t s) {
+  const PriTree& t = r->pri;
+  hipLaunchKernelGGL(pri_fill_range_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, t.level[0], start,
+                     rows, r->cap, t.d_max);
+  return pri_repair_ranges(t, start, rows, r->cap, s);
+}
+
+// Leaves [0, size) = max_priority, the rest 0, every parent recomputed.
+static int pri_reset(Ring* r, int64_t size, hipStream_t s) {
+  const PriTree& t = r->pri;
+  hipLaunchKernelGGL(pri_reset_kernel, dim3((unsigned)((t.len[0] + 255) / 256)), dim3(256), 0, s, t.level[0], size,
+                     t.len[0], t.d_max);
+  return pri_repair_ranges(t, 0, r->cap, r->cap, s);
+}
+
+int ring_store_priorities(Ring* r, const int64_t* idx, const float* p, int64_t n, bool td, hipStream_t s) {
+  const PriTree& t = r->pri;
+  hipLaunchKernelGGL(pri_clear_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.level[0], idx, n);
+  hipLaunchKernelGGL(pri_store_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.level[0], idx, p, n,
+                     td ? 1 : 0, (float)t.alpha, (float)t.eps, t.d_max);
+  for (int l = 1; l < t.levels; ++l)
+    hipLaunchKernelGGL(pri_repair_idx_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, t.level[l - 1],
+                       t.level[l], idx, n, 6 * l);
+  TD3_HIP(hipGetLastError());
+  return 0;
+}
+
+int ring_draw_prioritized(Ring* r, int batch, double beta, const float* inject_u, int64_t* idx_out,
+                          int64_t* idx_out2, float* weight_out, hipStream_t s) {
+  const PriTree& t = r->pri;
+  PriDrawArgs a{};
+  for (int l = 0; l < t.levels; ++l) a.level[l] = t.level[l];
+  a.levels = t.levels;
+  a.batch = batch;
+  a.cap = r->cap;
+  a.size = r->size;
+  a.beta = (float)beta;
+  a.inject_u = inject_u;
+  a.idx_out = idx_out;
+  a.idx_out2 = idx_out2;
+  a.w_raw = weight_out;                                            // normalised in place
+  a.seed = r->seed;
+  a.step = ++r->sample_calls;
+  hipLaunchKernelGGL(pri_draw_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(pri_normalise_kernel, dim3(1), dim3(256), 0, s, weight_out, weight_out, batch);
+  TD3_HIP(hipGetLastError());
+  return 0;
+}
+
 // After the launches that wrote `rows` rows at r->ptr.  Any write ends the n-step lane: the rows that
 // follow are not the next tick of it (an n-step add sets its lane again after this).
 static int ring_wrote(Ring* r, int64_t rows, int64_t new_size, hipStream_t s) {
+  if (r->pri.on && rows > 0) TD3_RC(pri_wrote(r, r->ptr, rows, s));
   r->ptr = (r->ptr + rows) % r->cap;
   r->size = new_size;
   r->ns_nhist = 0;
@@ -714,6 +947,8 @@ int rb_destroy(rb_handle* h) {
   (void)hipFree(r->data);
   (void)hipFree(r->d_size);
   (void)hipFree(r->d_idx);
+  (void)hipFree(r->pri.base);
+  (void)hipFree(r->pri.d_max);
   for (int* age : r->ns_age) (void)hipFree(age);
   for (int i = 0; i < 2; ++i) {
     if (r->stage_buf_ev[i]) (void)hipEventSynchronize(r->stage_buf_ev[i]);
@@ -1169,6 +1404,124 @@ int rb_sample_particles(rb_handle* h, int batch, float* feat, float* part, float
   return sample_fields(r, out, batch, inject_idx, idx_out, stream);
 }
 
+// ------------------------------------------------------------------ priorities (C-ABI)
+int rb_enable_priorities(rb_handle* h, double alpha, double eps, void* stream) {
+  TD3_ARG(alpha >= 0.0 && alpha <= 1.0, "alpha must be in [0, 1]");
+  TD3_ARG(eps > 0.0, "eps must be positive");
+  TD3_ARG(h != nullptr, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(!r->pri.on, "priorities are already enabled on this ring");
+  TD3_HIP(hipSetDevice(r->device));
+  PriTree t;
+  t.alpha = alpha;
+  t.eps = eps;
+  int64_t total = 0;
+  for (int64_t n = r->cap;; n = (n + 63) / 64) {      // n nodes at this level, padded to whole groups
+    TD3_ARG(t.levels < kMaxPriLevels, "max_size too large for the priority tree");
+    t.len[t.levels++] = (n + 63) / 64 * 64;
+    total += t.len[t.levels - 1];
+    if (n <= 64) break;
+  }
+  TD3_HIP(hipMalloc(&t.base, (size_t)total * sizeof(float)));
+  if (hipMalloc(&t.d_max, sizeof(float)) != hipSuccess) {
+    (void)hipFree(t.base);
+    set_error("rb_enable_priorities: hipMalloc failed");
+    return -2;
+  }
+  float* at = t.base;
+  for (int l = 0; l < t.levels; at += t.len[l++]) t.level[l] = at;
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  const float one = 1.0f;
+  TD3_HIP(hipMemsetAsync(t.base, 0, (size_t)total * sizeof(float), s));   // the pads stay zero for good
+  TD3_HIP(hipMemcpyAsync(t.d_max, &one, sizeof(float), hipMemcpyHostToDevice, s));
+  TD3_HIP(hipStreamSynchronize(s));                   // `one` is a pageable host source
+  t.on = true;
+  r->pri = t;
+  TD3_RC(ring_begin_write(r, s));
+  TD3_RC(pri_reset(r, r->size, s));
+  return ring_end_write(r, s);
+}
+
+// The checks shared by rb_set_priorities / rb_update_priorities; *r is set when there is work.
+static int priorities_args(rb_handle* h, const int64_t* idx, const float* p, int64_t n, Ring** r) {
+  *r = nullptr;
+  TD3_ARG(n >= 0, "n must be >= 0");
+  TD3_ARG(n == 0 || (idx && p), "null idx / priority array");
+  TD3_ARG(h != nullptr, "null handle");
+  TD3_ARG(reinterpret_cast<Ring*>(h)->pri.on, "priorities are not enabled on this ring (rb_enable_priorities)");
+  if (n > 0) *r = reinterpret_cast<Ring*>(h);
+  return 0;
+}
+
+static int store_priorities(Ring* r, const int64_t* idx, const float* p, int64_t n, bool td, void* stream) {
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_write(r, s));
+  TD3_RC(ring_store_priorities(r, idx, p, n, td, s));
+  return ring_end_write(r, s);
+}
+
+int rb_set_priorities(rb_handle* h, const int64_t* idx, const float* p, int64_t n, void* stream) {
+  Ring* r;
+  TD3_RC(priorities_args(h, idx, p, n, &r));
+  return r ? store_priorities(r, idx, p, n, false, stream) : 0;
+}
+
+int rb_update_priorities(rb_handle* h, const int64_t* idx, const float* td_abs, int64_t n, void* stream) {
+  Ring* r;
+  TD3_RC(priorities_args(h, idx, td_abs, n, &r));
+  return r ? store_priorities(r, idx, td_abs, n, true, stream) : 0;
+}
+
+int rb_sample_prioritized(rb_handle* h, int batch, double beta, const float* inject_u, int64_t* idx_out,
+                          float* weight_out, void* stream) {
+  TD3_ARG(batch > 0, "batch must be positive");
+  TD3_ARG(beta >= 0.0 && beta <= 1.0, "beta must be in [0, 1]");
+  TD3_ARG(idx_out && weight_out, "null idx_out / weight_out");
+  TD3_ARG(h != nullptr, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(h);
+  TD3_ARG(r->pri.on, "priorities are not enabled on this ring (rb_enable_priorities)");
+  TD3_ARG(r->size > 0, "sample from an empty buffer (size)");
+  TD3_HIP(hipSetDevice(r->device));
+  hipStream_t s = stream ? (hipStream_t)stream : r->stream;
+  TD3_RC(ring_begin_read(r, s));
+  TD3_RC(ring_draw_prioritized(r, batch, beta, inject_u, idx_out, nullptr, weight_out, s));
+  return ring_end_read(r, s);
+}
+
+int rb_get_priorities(const rb_handle* h, int64_t start, int64_t n, float* host_out) {
+  TD3_ARG(h && host_out, "null argument");
+  const Ring* r = reinterpret_cast<const Ring*>(h);
+  TD3_ARG(r->pri.on, "priorities are not enabled on this ring (rb_enable_priorities)");
+  TD3_ARG(start >= 0 && n >= 0 && start + n <= r->cap, "range out of bounds");
+  TD3_HIP(hipSetDevice(r->device));
+  TD3_HIP(hipDeviceSynchronize());
+  TD3_HIP(hipMemcpy(host_out, r->pri.level[0] + start, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int rb_priority_info(const rb_handle* h, rb_priority_info_t* info) {
+  TD3_ARG(h && info, "null argument");
+  const Ring* r = reinterpret_cast<const Ring*>(h);
+  const PriTree& t = r->pri;
+  *info = rb_priority_info_t{};
+  if (!t.on) return 0;
+  info->enabled = 1;
+  info->alpha = t.alpha;
+  info->eps = t.eps;
+  info->levels = t.levels;
+  TD3_HIP(hipSetDevice(r->device));
+  TD3_HIP(hipDeviceSynchronize());
+  float root[64];
+  TD3_HIP(hipMemcpy(root, t.level[t.levels - 1], sizeof(root), hipMemcpyDeviceToHost));
+  TD3_HIP(hipMemcpy(&info->max_priority, t.d_max, sizeof(float), hipMemcpyDeviceToHost));
+  // the sum a draw takes over the root group: lane 63 of pri_group_scan adds neighbours pairwise
+  for (int w = 1; w < 64; w <<= 1)
+    for (int i = 0; i < 64; i += 2 * w) root[i] = root[i] + root[i + w];
+  info->total = (double)root[0];
+  return 0;
+}
+
 int rb_read_records(const rb_handle* h, int64_t start, int64_t n, float* out) {
   TD3_ARG(h && out, "null argument");
   const Ring* r = reinterpret_cast<const Ring*>(h);
@@ -1195,6 +1548,10 @@ int rb_write_records(rb_handle* h, int64_t start, int64_t n, const float* in, in
   r->size = size;
   r->ns_nhist = 0;                                   // the n-step lane ends with any other write
   TD3_HIP(hipMemcpy(r->d_size, &r->size, sizeof(int64_t), hipMemcpyHostToDevice));
+  if (r->pri.on) {                                   // the loaded rows are new rows: max_priority each
+    TD3_RC(pri_reset(r, r->size, r->stream));
+    TD3_HIP(hipStreamSynchronize(r->stream));
+  }
   return 0;
 }
 

@@ -248,6 +248,11 @@ struct Plan {
   float* W1aT = nullptr;
   int64_t* d_idx = nullptr;
   int64_t* d_inject_idx = nullptr;
+  // featured: the rows' importance weights in the critic loss (target_loss::kW), ones unless the last
+  // step was prioritized (per_w_dirty: the next other step refills them, ensure_unit_weights), the
+  // rows' |TD error| (kTd) and the injected mass fractions of a prioritized draw
+  float *per_w = nullptr, *per_td = nullptr, *per_u = nullptr;
+  bool per_w_dirty = false;
   EvalB TA, Q[2], A, TQ[2], AQ;
   // device problem tables (owned)
   std::vector<void*> tables;
@@ -406,6 +411,7 @@ struct td3_handle {
   // td3_probe_kernel: while set, steps launch directly and every stage launching `probe_kernel` is
   // bracketed by a pair of HIP events on the step's stream (probe_ev[2k], probe_ev[2k + 1])
   bool probing = false;
+  bool per_step = false;                      // inside td3_train_step_prioritized: the body keeps its weights
   std::string probe_kernel;
   std::vector<hipEvent_t> probe_ev;
   int probe_used = 0;
@@ -1656,7 +1662,7 @@ static int build_step(td3_handle* h, int B) {
   const NetL& an = h->actor.nets[0];
   const NetL& q1 = h->critic.nets[0];
   const NetL& q2 = h->critic.nets[1];
-  size_t floats = (size_t)Bp * 3 * P->ld_sa + 10 * (size_t)Bp + (size_t)Bp * ad + 4096 + (size_t)ad * q1.lin[0].Np;
+  size_t floats = (size_t)Bp * 3 * P->ld_sa + 13 * (size_t)Bp + (size_t)Bp * ad + 4096 + 192 + (size_t)ad * q1.lin[0].Np;
   floats += eval_floats(an, Bp, false, norm) + 2 * eval_floats(q1, Bp, true, norm) +
             eval_floats(an, Bp, true, norm) + 2 * eval_floats(q1, Bp, false, norm) +
             eval_floats(q1, Bp, true, norm) + 1024;
@@ -1680,6 +1686,13 @@ static int build_step(td3_handle* h, int B) {
   P->d_inject_idx = (int64_t*)S.take(2 * (size_t)Bp);
   P->gscale[0] = S.take(Bp);
   P->gscale[1] = S.take(Bp);
+  P->per_w = S.take(Bp);
+  P->per_td = S.take(Bp);
+  P->per_u = S.take(Bp);
+  {
+    const std::vector<float> ones((size_t)Bp, 1.0f);
+    TD3_HIP(hipMemcpy(P->per_w, ones.data(), (size_t)Bp * sizeof(float), hipMemcpyHostToDevice));
+  }
   P->W1aT = S.take((size_t)ad * q1.lin[0].Np);
   alloc_eval(S, an, Bp, P->X_S2A, P->ld_sa, false, norm, false, P->TA);
   alloc_eval(S, q1, Bp, P->X_SA, P->ld_sa, true, norm, true, P->Q[0]);
@@ -1783,6 +1796,8 @@ static int build_step(td3_handle* h, int B) {
         p.ex[tl::kNotDone] = P->ND;
         p.ex[tl::kY] = P->Y;
         p.ex[tl::kSqErr] = P->sqerr;
+        p.ex[tl::kW] = P->per_w;
+        p.ex[tl::kTd] = P->per_td;
         p.exi[tl::kK3] = q1.lin[2].N;
         p.exi[tl::kLd3] = q1.lin[2].Np;
         p.exf[tl::kDiscount] = (float)h->cfg.discount;
@@ -2306,6 +2321,21 @@ static int input_from_batch(td3_handle* h, Plan* P, const float* s, const float*
   return 0;
 }
 
+// Unit importance weights for a step that is not prioritized: refilled on its stream, ahead of its
+// body, only when a prioritized step overwrote them (a host flag: the common path queues nothing).
+__global__ void fill_f32_kernel(float* p, int n, float v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+static int ensure_unit_weights(td3_handle* h, hipStream_t s) {
+  Plan* P = h->plan.get();
+  if (!P->per_w_dirty || h->per_step) return 0;
+  hipLaunchKernelGGL(fill_f32_kernel, dim3((P->Bp + 255) / 256), dim3(256), 0, s, P->per_w, P->Bp, 1.0f);
+  TD3_HIP(hipGetLastError());
+  P->per_w_dirty = false;
+  return 0;
+}
+
 // One step body on stream s.  With `ring` set, the replay-ring gather (Philox draw) is
 // launched first and, in graph mode, captured into the same hipGraph (one replay per step).
 static int run_body(td3_handle* h, int actor_phase, int inj, hipStream_t s, Ring* ring) {
@@ -2314,6 +2344,7 @@ static int run_body(td3_handle* h, int actor_phase, int inj, hipStream_t s, Ring
     return -1;
   }
   TD3_RC(ensure_w4(h, s));
+  TD3_RC(ensure_unit_weights(h, s));
   Plan* P = h->plan.get();
   const bool fused = ring && P->fuse_gather;     // featured: the sample runs inside F_fwd0
   std::vector<Stage>& st = fused ? P->body_ring[actor_phase][inj] : P->body[actor_phase][inj];
@@ -3252,6 +3283,49 @@ int td3_train_step(td3_handle* h, rb_handle* rbh, int batch, void* stream, const
   return finish_step(h, actor_phase, s, stats);
 }
 
+int td3_train_step_prioritized(td3_handle* h, rb_handle* rbh, int batch, double beta, void* stream,
+                               const float* inject_u, const float* inject_noise, td3_step_stats* stats,
+                               td3_per_stats* per) {
+  TD3_ARG(h && rbh, "null handle");
+  TD3_ARG(batch > 0, "batch must be positive");
+  TD3_ARG(beta >= 0.0 && beta <= 1.0, "beta must be in [0, 1]");
+  TD3_ARG(!h->particles, "td3_train_step_prioritized on a particle learner (its loss takes no importance weights)");
+  TD3_ARG(!h->comm && !h->local, "td3_train_step_prioritized on a data-parallel handle (comm group attached)");
+  Ring* r = reinterpret_cast<Ring*>(rbh);
+  TD3_ARG(r->particles == h->particles, "replay buffer kind does not match the learner");
+  TD3_ARG(r->sd == h->sd && r->ad == h->ad, "replay buffer dims do not match the learner");
+  TD3_ARG(r->device == h->cfg.device, "replay buffer lives on another device");
+  TD3_ARG(r->pri.on, "priorities are not enabled on this ring (rb_enable_priorities)");
+  TD3_ARG(r->size > 0, "train on an empty replay buffer");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_RC(ensure_plan(h, batch));
+  Plan* P = h->plan.get();
+  TD3_RC(bind_ring(h, r));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  TD3_RC(ring_begin_read(r, s));                 // one section: draw, gather, body, priority write-back
+  if (inject_u) TD3_HIP(hipMemcpyAsync(P->per_u, inject_u, (size_t)batch * 4, hipMemcpyHostToDevice, s));
+  if (inject_noise)
+    TD3_HIP(hipMemcpyAsync(P->noise, inject_noise, (size_t)batch * h->ad * 4, hipMemcpyHostToDevice, s));
+  const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
+  P->per_w_dirty = true;
+  TD3_RC(ring_draw_prioritized(r, batch, beta, inject_u ? P->per_u : nullptr, P->d_inject_idx, P->d_idx, P->per_w, s));
+  TD3_RC(input_from_ring(h, r, P, true, s));
+  h->per_step = true;
+  const int rc = run_body(h, actor_phase, inject_noise ? 1 : 0, s, nullptr);
+  h->per_step = false;
+  TD3_RC(rc);
+  TD3_RC(ring_store_priorities(r, P->d_inject_idx, P->per_td, batch, true, s));
+  TD3_RC(ring_end_read(r, s));                   // later adds wait for the step and its write-back
+  if (inject_u || inject_noise) TD3_HIP(hipStreamSynchronize(s));   // host sources are pageable
+  TD3_RC(finish_step(h, actor_phase, s, stats));
+  if (per && (per->weight || per->td_abs)) {
+    TD3_HIP(hipStreamSynchronize(s));
+    if (per->weight) TD3_HIP(hipMemcpy(per->weight, P->per_w, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    if (per->td_abs) TD3_HIP(hipMemcpy(per->td_abs, P->per_td, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
 int td3_train_step_batch(td3_handle* h, const float* state, const float* action, const float* next_state,
                          const float* reward, const float* not_done, int batch, void* stream,
                          const float* inject_noise, td3_step_stats* stats) {
@@ -3811,6 +3885,7 @@ int td3_train_step_local(td3_handle** hs, rb_handle** rbs, int n, int batch, con
     if (h->stream != s) TD3_HIP(hipStreamSynchronize(h->stream));
     TD3_RC(ensure_plan(h, batch));
     TD3_RC(ensure_w4(h, s));
+    TD3_RC(ensure_unit_weights(h, s));
     TD3_RC(bind_ring(h, r));
     TD3_RC(ring_begin_read(r, s));
   }
@@ -3913,6 +3988,7 @@ int td3_profile_stages(td3_handle* h, rb_handle* rbh, int batch, int actor_phase
   for (auto& e : ev) TD3_HIP(hipEventCreate(&e));
   hipStream_t s = h->stream;
   TD3_RC(ensure_w4(h, s));
+  TD3_RC(ensure_unit_weights(h, s));
   TD3_RC(ring_begin_read(r, s));
   TD3_HIP(hipEventRecord(ev[0], s));
   if (!fused) TD3_RC(input_from_ring(h, r, P, false, s));

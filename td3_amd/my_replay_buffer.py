@@ -213,6 +213,7 @@ class _RingBuffer(object):
         self.seed = int(seed)
         self._h = None
         self._n = 0
+        self._per = None                         # (alpha, eps) once enable_priorities was called
         if load_folder is not None:
             self.load(load_folder)
         else:
@@ -243,6 +244,8 @@ class _RingBuffer(object):
         self._stage_ptr = _lib.fptr(self._stage)
         self._n = 0
         self._shadow = _HostShadow.zeros(self._shapes(max_size)) if self.host_shadow else None
+        if self._per is not None:                # a ring re-created by load() keeps its priorities on
+            self._call("rb_enable_priorities", self._h, *self._per, self._stream())
 
     def _shapes(self, n):
         return {name: (n, *shape) for name, _, shape in self._fields}
@@ -380,6 +383,81 @@ class _RingBuffer(object):
         if return_indices:
             return out, idx_out
         return out
+
+    # ------------------------------------------------------------------ priorities
+    def enable_priorities(self, alpha=0.6, eps=1e-6):
+        """Prioritized replay (Schaul et al. 2016): per-row priorities in a sum tree next to the ring
+        (``rb_enable_priorities``).  The rows already stored get priority 1, every row added later the
+        largest priority stored so far; ``TD3.train`` then draws rows in proportion to their
+        priorities, weights the critic loss and writes ``(|TD error| + eps) ** alpha`` back.  The
+        arguments are remembered: ``load()`` re-creates the ring and enables them again (all loaded
+        rows then have one priority; ``save()`` does not store priorities)."""
+        self.flush()
+        self._call("rb_enable_priorities", self._h, float(alpha), float(eps), self._stream())
+        self._per = (float(alpha), float(eps))
+
+    @property
+    def prioritized(self):
+        return self._per is not None
+
+    def sample_prioritized(self, batch_size, beta, u=None):
+        """``(idx, weights)``: int64 rows drawn in proportion to their priorities (stratified: draw k
+        from the k-th of ``batch_size`` equal slices of the total mass) and their importance weights
+        ``(size * p / total) ** -beta``, normalised by the largest of the batch; CUDA tensors.  ``u``
+        (``[batch_size]`` mass fractions in [0, 1)) replaces the Philox draw."""
+        torch = _torch()
+        self.flush()
+        B = int(batch_size)
+        idx = torch.empty((B,), device=self.device, dtype=torch.int64)
+        w = torch.empty((B,), device=self.device, dtype=torch.float32)
+        inj = None
+        if u is not None:
+            inj = torch.as_tensor(u, device=self.device).to(torch.float32).reshape(-1).contiguous()
+            if inj.numel() != B:
+                raise ValueError("u must have batch_size entries")
+        with self._torch_order():
+            self._call("rb_sample_prioritized", self._h, B, float(beta),
+                       inj.data_ptr() if inj is not None else None, idx.data_ptr(), w.data_ptr(), self._stream())
+        return idx, w
+
+    def _store_priorities(self, call, idx, values):
+        torch = _torch()
+        self.flush()
+        if not (_is_cuda_tensor(idx) and _is_cuda_tensor(values)):
+            raise TypeError(f"{call} takes CUDA tensors (indices and values stay on the device)")
+        i = idx.to(self.device, torch.int64).reshape(-1).contiguous()
+        v = values.to(self.device, torch.float32).reshape(-1).contiguous()
+        if i.numel() != v.numel():
+            raise ValueError(f"{call}: idx and values must have the same number of entries")
+        if i.numel() == 0:                       # an empty tensor has no address
+            self._call(call, self._h, None, None, 0, self._stream())
+            return
+        with self._torch_order():                # as _add_batch_device: i and v live until the exit
+            self._call(call, self._h, i.data_ptr(), v.data_ptr(), i.numel(), self._stream())
+
+    def update_priorities(self, idx, td_abs):
+        """Priorities of rows ``idx`` = ``(td_abs + eps) ** alpha`` (CUDA tensors; ``rb_update_priorities``)."""
+        self._store_priorities("rb_update_priorities", idx, td_abs)
+
+    def set_priorities(self, idx, p):
+        """Priorities of rows ``idx`` = ``p`` as given, finite and >= 0 (CUDA tensors); 0 takes a row
+        out of the draw."""
+        self._store_priorities("rb_set_priorities", idx, p)
+
+    def priorities(self):
+        """The priority of every ring row, numpy ``[max_size]`` (0 for rows never written)."""
+        self.flush()
+        out = np.empty((self.max_size,), dtype=np.float32)
+        check(self._lib.rb_get_priorities(self._h, 0, self.max_size, _lib.fptr(out)), "rb_get_priorities")
+        return out
+
+    def priority_info(self):
+        """``dict`` of enabled, alpha, eps, levels (of the tree), total (the sum of all priorities as
+        the draw sees it) and max_priority (what a new row receives)."""
+        self.flush()
+        info = _lib.rb_priority_info_t()
+        check(self._lib.rb_priority_info(self._h, info), "rb_priority_info")
+        return {k: getattr(info, k) for k, _ in info._fields_}
 
     # ------------------------------------------------------------------ persistence
     def _records(self):
