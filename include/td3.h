@@ -34,6 +34,10 @@
  *   td3_train_step_prioritized
  *                        prioritized experience replay on the device ring (no counterpart in the
  *                        reference): a 64-ary sum tree next to the ring, the weighted critic loss
+ *   rs_create / rs_tick / rs_get_state / rs_set_state / rs_read_episodes / rs_info
+ *                        rollout statistics of a GPU-resident vector environment (no counterpart in the
+ *                        reference): running observation / reward normalisation and the episode log,
+ *                        one launch per tick
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -259,6 +263,118 @@ int rb_sample_prioritized(rb_handle* h, int batch, double beta, const float* inj
                           float* weight_out, void* stream);
 int rb_get_priorities(const rb_handle* h, int64_t start, int64_t n, float* host_out);
 int rb_priority_info(const rb_handle* h, rb_priority_info_t* info);
+
+/* ------------------------------------------------------------------ rollout statistics */
+/* Per-tick bookkeeping of a GPU-resident vector environment (no counterpart in the reference; what gym's
+ * NormalizeObservation / NormalizeReward wrappers and main.py:240-289's episode prints do on the host):
+ * running observation moments and normalisation, running moments of the discounted return and reward
+ * scaling, and a log of finished episodes -- none of it read back per tick.  An rs_handle owns, for `rows`
+ * environments of `obs_dim` columns, all in device memory:
+ *   observation moments  count, mean[obs_dim], m2[obs_dim]                       (fp64)
+ *   return moments       ret_count, ret_mean, ret_m2, the accumulator G[rows]    (fp64)
+ *   episode accounting   ep_return[rows] (fp64), ep_len[rows] (int32)
+ *   episode log          a ring of log_cap rs_episode entries; ep_count, ep_len_sum, tick (int64),
+ *                        ep_return_sum (fp64)
+ * It touches neither a learner nor a replay ring: the rows a caller stores are simply the normalised ones.
+ * fp64 throughout: a running mean over 10^8 rows of columns spanning orders of magnitude loses what fp32
+ * carries, fp64 vector arithmetic is cheap on this part, and the data of a tick is a few hundred KB.
+ *
+ * rs_tick is one call per environment tick and EXACTLY ONE KERNEL LAUNCH (rs_tick_kernel; none when no
+ * input is given): asynchronous on `stream`, no host read-back, no allocation.  Unlike the ring and
+ * learner calls a NULL `stream` is HIP's default (null) stream itself -- the handle owns no stream; torch's
+ * default stream is that one, so a tick queued there is ordered with the torch ops around it.
+ * Device inputs (each nullable): obs [rows][obs_dim], the rows the next actions are chosen from (after
+ * auto-reset); next_obs [rows][obs_dim], the transition's own next state; reward [rows]; ended [rows]
+ * (nonzero: the row's episode ended with this transition).  Device outputs (each nullable, each may alias
+ * its own input and nothing else): obs_out, next_obs_out, reward_out.  In this order:
+ *  1. Observation moments, only with update = 1 and obs given.  Per enabled column: the batch sum, then
+ *     mb = sum / rows, then m2b = sum (x - mb)^2, in fp64 and in an order fixed by (rows, obs_dim): column
+ *     c is summed by P = 1024 / W row phases, phase p over rows p, p + P, ... in row order, the phases
+ *     combined by a halving tree (p += p + s, s = P/2, ..., 1); W is the largest power of two <= 64 with
+ *     rows * W <= 8192 (at least 1), halved while W / 2 >= obs_dim, and a workgroup owns W columns.
+ *     Chan's merge: d = mb - mean, tot = count + rows, mean += d * rows / tot,
+ *     m2 += m2b + d * d * count * rows / tot, count = tot.  No float atomics: runs repeat bit for bit.
+ *  2. Normalise obs and next_obs where given with an output, both with the moments as they stand after 1:
+ *     an enabled column gets out = (float) clip((x - mean) / sqrt(m2 / count + obs_eps), +-obs_clip),
+ *     evaluated in fp64 and rounded to fp32 once; with count == 0 and in a masked column out = x bit for bit.
+ *  3. Reward, only with reward given.  G_i = gamma * G_i + r_i.  With update = 1 the batch moments of G over
+ *     the rows (row i in partial i mod 1024, the partials by the same halving tree) are merged into the
+ *     return moments by the same formula.  reward_out_i = (float) clip(r_i / sqrt(ret_m2 / ret_count +
+ *     rew_eps), +-rew_clip) in fp64 (r_i itself while ret_count == 0).  Then G_i = 0 where ended_i.
+ *  4. Episodes, whenever reward is given, whatever `update`: ep_return_i += r_i (the raw reward),
+ *     ep_len_i += 1; for the rows with ended_i IN INCREASING ROW ORDER the entry {(float) ep_return_i,
+ *     ep_len_i, i, tick} goes to log slot ep_count mod log_cap, ep_count += 1, ep_return_sum += ep_return_i,
+ *     ep_len_sum += ep_len_i, and the row's two accumulators are zeroed.  Then tick += 1 (a call without a
+ *     reward, e.g. the one after reset(), is not a tick).
+ * update = 0 freezes every moment (evaluation); episodes are still logged.
+ * rs_config.col_mask (host uint8 [obs_dim], nullable, read during rs_create only): a zero takes the column
+ * out of normalisation -- copied through bit for bit, no moments kept -- e.g. the goal columns a hindsight
+ * relabel overwrites with raw goals.
+ * rs_get_state / rs_set_state: every moment, accumulator, counter and the whole log ring to / from host
+ * arrays of the caller (mean, m2 [obs_dim]; G, ep_return, ep_len [rows]; log [log_cap], slot order);
+ * synchronous (they wait for the device), for checkpoints.  rs_read_episodes: the entries with sequence
+ * numbers in [first, first + n) that are still in the ring (the last log_cap), oldest first, into out;
+ * *first_out is the sequence number of out[0], *n_out the entries written; synchronous.  rs_info: synchronous.
+ * A caller's stream must stay alive until its ticks have completed.  Handles are not re-entrant.
+ * Checked in this order, each failure returning -1 before any GPU work with a message naming the field:
+ *   rs_create: out; rows in 1..2^24; obs_dim in 1..2^20; log_cap in 1..2^24; cfg non-null; cfg->obs_eps
+ *     (finite, >= 0); cfg->obs_clip (finite, > 0); cfg->rew_eps; cfg->rew_clip; cfg->gamma in [0, 1].
+ *   rs_tick: a non-null; a->update 0 or 1; a->obs_out without a->obs; a->next_obs_out without a->next_obs;
+ *     a->reward_out without a->reward; a->ended without a->reward; the handle.
+ *   rs_get_state: st non-null; st->mean, m2, G, ep_return, ep_len, log non-null, in this order; the handle.
+ *   rs_set_state: the same, then st->count, st->ret_count (finite, >= 0), st->ep_count, st->ep_len_sum,
+ *     st->tick (>= 0); the handle.
+ *   rs_read_episodes: first >= 0; n >= 0; out non-null unless n == 0; first_out; n_out; the handle.
+ *   rs_info: info non-null; the handle.   rs_destroy(NULL) returns 0. */
+typedef struct rs_handle rs_handle;
+typedef struct rs_config {
+  double obs_eps, obs_clip;      /* gym's NormalizeObservation: 1e-8, 10 */
+  double rew_eps, rew_clip;      /* gym's NormalizeReward: 1e-8, 10 */
+  double gamma;                  /* discount of the return whose spread scales the reward */
+  const uint8_t* col_mask;       /* host [obs_dim], nullable: 0 -> the column is passed through */
+} rs_config;
+typedef struct rs_tick_t {
+  const float* obs;              /* device [rows][obs_dim], nullable */
+  const float* next_obs;         /* device [rows][obs_dim], nullable */
+  const float* reward;           /* device [rows], nullable */
+  const uint8_t* ended;          /* device [rows], nullable (needs reward) */
+  float* obs_out;                /* device, nullable, may be obs */
+  float* next_obs_out;           /* device, nullable, may be next_obs */
+  float* reward_out;             /* device, nullable, may be reward */
+  int update;                    /* 1: steps 1 and 3 update the moments; 0: frozen */
+} rs_tick_t;
+typedef struct rs_episode {
+  float ret;                     /* the episode's undiscounted return (raw rewards) */
+  int32_t len;                   /* its length in ticks */
+  int32_t row;                   /* the environment */
+  int32_t reserved;              /* 0 */
+  int64_t tick;                  /* the tick it ended at */
+} rs_episode;
+typedef struct rs_info_t {
+  int rows, obs_dim, log_cap, device;
+  int64_t ep_count, ep_len_sum, tick;
+  double ep_return_sum, count, ret_count;
+} rs_info_t;
+typedef struct rs_state {
+  double count;
+  double* mean;                  /* host [obs_dim] */
+  double* m2;                    /* host [obs_dim] */
+  double ret_count, ret_mean, ret_m2;
+  double* G;                     /* host [rows] */
+  double* ep_return;             /* host [rows] */
+  int32_t* ep_len;               /* host [rows] */
+  rs_episode* log;               /* host [log_cap], slot order */
+  int64_t ep_count, ep_len_sum, tick;
+  double ep_return_sum;
+} rs_state;
+int rs_create(int rows, int obs_dim, int log_cap, int device, const rs_config* cfg, rs_handle** out);
+int rs_destroy(rs_handle* h);
+int rs_tick(rs_handle* h, const rs_tick_t* a, void* stream);
+int rs_info(const rs_handle* h, rs_info_t* info);
+int rs_get_state(const rs_handle* h, rs_state* st);
+int rs_set_state(rs_handle* h, const rs_state* st);
+int rs_read_episodes(const rs_handle* h, int64_t first, int64_t n, rs_episode* out, int64_t* first_out,
+                     int64_t* n_out);
 
 /* ------------------------------------------------------------------ learner */
 /* struct_size:sizeof(td3_config) as the caller compiled it.  td3_default_config sets it and

@@ -63,6 +63,36 @@ class td3_per_stats(C.Structure):
     _fields_ = [("weight", C.c_void_p), ("td_abs", C.c_void_p)]
 
 
+class rs_config(C.Structure):
+    _fields_ = [("obs_eps", C.c_double), ("obs_clip", C.c_double), ("rew_eps", C.c_double),
+                ("rew_clip", C.c_double), ("gamma", C.c_double), ("col_mask", C.c_void_p)]
+
+
+class rs_tick_t(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("next_obs", C.c_void_p), ("reward", C.c_void_p), ("ended", C.c_void_p),
+                ("obs_out", C.c_void_p), ("next_obs_out", C.c_void_p), ("reward_out", C.c_void_p),
+                ("update", C.c_int)]
+
+
+class rs_episode(C.Structure):
+    _fields_ = [("ret", C.c_float), ("len", C.c_int32), ("row", C.c_int32), ("reserved", C.c_int32),
+                ("tick", C.c_int64)]
+
+
+class rs_info_t(C.Structure):
+    _fields_ = [("rows", C.c_int), ("obs_dim", C.c_int), ("log_cap", C.c_int), ("device", C.c_int),
+                ("ep_count", C.c_int64), ("ep_len_sum", C.c_int64), ("tick", C.c_int64),
+                ("ep_return_sum", C.c_double), ("count", C.c_double), ("ret_count", C.c_double)]
+
+
+class rs_state(C.Structure):
+    _fields_ = [("count", C.c_double), ("mean", C.c_void_p), ("m2", C.c_void_p),
+                ("ret_count", C.c_double), ("ret_mean", C.c_double), ("ret_m2", C.c_double),
+                ("G", C.c_void_p), ("ep_return", C.c_void_p), ("ep_len", C.c_void_p), ("log", C.c_void_p),
+                ("ep_count", C.c_int64), ("ep_len_sum", C.c_int64), ("tick", C.c_int64),
+                ("ep_return_sum", C.c_double)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -92,6 +122,13 @@ SIGNATURES = {
     "rb_sample_prioritized": (C.c_int, [_P, C.c_int, C.c_double, _P, _P, _P, _P]),
     "rb_get_priorities": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
     "rb_priority_info": (C.c_int, [_P, C.POINTER(rb_priority_info_t)]),
+    "rs_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(rs_config), C.POINTER(_P)]),
+    "rs_destroy": (C.c_int, [_P]),
+    "rs_tick": (C.c_int, [_P, C.POINTER(rs_tick_t), _P]),
+    "rs_info": (C.c_int, [_P, C.POINTER(rs_info_t)]),
+    "rs_get_state": (C.c_int, [_P, C.POINTER(rs_state)]),
+    "rs_set_state": (C.c_int, [_P, C.POINTER(rs_state)]),
+    "rs_read_episodes": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(rs_episode), _I64, _I64]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
     "rb_write_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F, C.c_int64, C.c_int64]),
     "rb_sync": (C.c_int, [_P]),

@@ -32,7 +32,9 @@ query's encoder reads the simulator's particle tensor in place.  With ``relabel=
 ``SyntheticGoalVecEnv``) each tick's transitions and their K relabels are stored by one fan-out add
 (``add_batch_hindsight``): the relabelled rows are never built outside the ring.  With ``n_step=n``
 each tick is stored by ``add_batch_nstep``: the rows of the previous n - 1 ticks mature in the ring into
-multi-step transitions (include/td3.h), the train step unchanged.
+multi-step transitions (include/td3.h), the train step unchanged.  ``rollout_stats.NormalizedVecEnv``
+around any of these environments adds running observation / reward normalisation and an episode log
+kept on the device (one launch per tick); ``log_every`` / ``on_log`` are where the loop reads it.
 """
 from __future__ import annotations
 
@@ -351,10 +353,14 @@ class DeviceTrainLoop:
     ``n_step`` > 1 stores each tick through ``add_batch_nstep(..., ended=done, n=n_step,
     gamma=policy.discount)``: the rows of the previous ``n_step - 1`` ticks mature in the ring into
     multi-step transitions, with no read-back of ``done``.  The stored ``done`` is still ``done_bool``,
-    so a time-limit end under ``done_swap`` bootstraps and stops maturing.  Not with ``relabel=``."""
+    so a time-limit end under ``done_swap`` bootstraps and stops maturing.  Not with ``relabel=``.
+
+    ``on_log(t, loop)``, when given with ``log_every`` > 0, is called after every ``log_every``-th tick
+    (``t`` counts the ticks done): the place to read ``rollout_stats.RolloutStats.summary()`` of a
+    ``NormalizedVecEnv`` or to evaluate.  What it reads back is its own cost; off by default."""
 
     def __init__(self, env, policy, replay_buffer, *, start_policy, start_training, batch_size, expl_noise,
-                 done_swap=True, train_steps_per_tick=1, seed=0, relabel=None, n_step=1):
+                 done_swap=True, train_steps_per_tick=1, seed=0, relabel=None, n_step=1, log_every=0, on_log=None):
         from .exploration import DeviceOUNoise
         self.n_step = int(n_step)
         if self.n_step < 1:
@@ -367,6 +373,7 @@ class DeviceTrainLoop:
         self.done_swap = done_swap
         self.train_steps_per_tick = int(train_steps_per_tick)
         self.relabel = relabel
+        self.log_every, self.on_log = int(log_every), on_log
         self.max_action = float(policy.max_action)
         self.noise = DeviceOUNoise(env.n_envs, policy.action_dim, sigma=expl_noise, device=policy.device,
                                    seed=seed)
@@ -401,6 +408,8 @@ class DeviceTrainLoop:
                 for _ in range(self.train_steps_per_tick):
                     policy.train(rb, self.batch_size)
                     grad_steps += 1
+            if self.on_log is not None and self.log_every > 0 and (t + 1) % self.log_every == 0:
+                self.on_log(t + 1, self)
         policy.sync()
         torch.cuda.synchronize(policy.device)
         dt = time.perf_counter() - t0
