@@ -605,7 +605,7 @@ double td3_stage_bytes(td3_handle* h, int i);
  * zero the oracle and the GPU may both be right about opposite masks (tests/test_gpu_gradients.py). */
 int td3_debug_activation(td3_handle* h, int eval, int layer, float* out, int rows, int cols);
 /* Test instrumentation: properties of the current step plan (0 before the first step): bit 0 = the forward
- * GEMM stages read the k-quad weight images (td3.hip Group::P4 / T4; TD3_W4 != 0, every featured plan
+ * GEMM stages read the k-quad weight images (learner.h Group::P4 / T4; TD3_W4 != 0, every featured plan
  * except weight normalization -- any batch size, data-parallel plans included; particle learners never),
  * bit 1 = the plan's optimizer steps are sharded over ranks.  A rebuild that leaves a sharded schedule
  * gathers the Adam moments first (collective on RCCL ranks, as td3_dp_gather_optimizer_state). */

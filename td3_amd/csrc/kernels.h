@@ -2,6 +2,8 @@
 // loads by every workgroup; pointers are fixed for the handle's life so the launches can
 // be captured once into a hipGraph and replayed).
 #pragma once
+#include <initializer_list>
+
 #include "common.h"
 
 #ifndef TD3_GEMM_WAVES
@@ -54,7 +56,7 @@ enum RowKind : int {
 
 // ------------------------------------------------------------------ operand slots
 // GemmProb::ex (pointers) / exi (ints) / exf (floats) by kind: every kind names its slots here, once
-// for the kernels (kernels.hip) and the host planner (td3.hip).  Per kind: pointer slots, integer
+// for the kernels (kernels.hip) and the host planner (stages.hip, step.hip).  Per kind: pointer slots, integer
 // slots, float slots, each enum closed by its slot count.  "x3" / "x2" slots are consecutive, one
 // per network, indexed kName + n.
 constexpr int kMaxEx = 24;
@@ -391,7 +393,7 @@ struct GemmProb {
   int B;                          // real batch rows (rows >= B are padding)
   // MODE 0 weight image: the 16-B piece W[n][4j .. 4j+3] is at W + n * ldw + j * wsk.  Row-major
   // [n][Kp] (the parameter arena): ldw = Kp, wsk = 4 (0 reads as 4).  The k-quad image [Kp/4][Np][4]
-  // (td3.hip Group::P4 / T4): ldw = 4, wsk = 4 * Np -- the 16 lanes of an MFMA fragment load (16 or 32
+  // (learner.h Group::P4 / T4): ldw = 4, wsk = 4 * Np -- the 16 lanes of an MFMA fragment load (16 or 32
   // consecutive n, one k-quad) read 256 contiguous bytes instead of 16 rows' pieces.
   int wsk;
   int w0sk;                       // kProL0*: the same for W0 (ring_l0::kW0): 0 = row-major [N0p][32]
@@ -528,7 +530,7 @@ enum DwMode : int { kDwGrad = 0, kDwAdam = 1, kDwAdamPolyak = 2 };
 struct AdamArgs {
   float* P; float* G; float* M; float* V; float* T;   // group arenas
   // nullable: the k-quad images of P / T (GemmProb::wsk) that the forward GEMM stages read; dw_kernel
-  // writes every updated weight element to them too (td3.hip Group::P4 / T4)
+  // writes every updated weight element to them too (learner.h Group::P4 / T4)
   float* P4; float* T4;
   const Counters* ctr; int which;                     // 0: critic_step, 1: actor_step
   double lr, beta1, beta2, eps;
@@ -645,6 +647,10 @@ struct W4PackArgs {
   int nmat;
 };
 int launch_w4_pack(const W4PackArgs& a, hipStream_t s);
+// pack_kernel: the [B][cols] rows of src into columns [col, col + cols) of up to three ld-strided
+// destinations (a null p is skipped), zeros for rows B .. Bp - 1; one workgroup per row of Bp
+struct PackDst { float* p; int ld, col; };
+int launch_pack(const float* src, int cols, int B, int Bp, std::initializer_list<PackDst> dst, hipStream_t s);
 // Epilogue of td3_select_action_device: the policy head's rows pi (max_action * tanh, row stride ldp)
 // -> action_out [n][ad].  plain: a copy.  Otherwise z ~ N(0,1) (Philox kStreamExplore, or inject_z),
 // x != null: the Ornstein-Uhlenbeck state X <- X + (theta (mu - X) + sigma z) (X = mu first where

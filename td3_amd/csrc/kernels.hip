@@ -569,7 +569,7 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
   const bool target = P.exi[kTarget] != 0;
   const float ma = P.exf[kMaxAction];
   const bool gen = target && P.exi[kGenNoise];
-  // the counter (ctr is always set, td3.hip) by an ordinary relaxed load whose address carries a
+  // the counter (ctr is always set, step.hip policy_head_prob) by an ordinary relaxed load whose address carries a
   // lane-dependent zero (mbcnt with an empty mask): a divergent load, so the value lands in VGPRs
   // and the compiler's own wait placement defers it to the Philox draw.  Left uniform, it is a
   // scalar load waited for ahead of the row's loads.
@@ -1272,7 +1272,7 @@ __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, in
   static_assert(RT == 1 || (PRO != kProL0 && PRO != kProL0G && PRO != kProGather), "two row tiles: plain prologues");
   // WN = 0: 16 output columns per workgroup on v_mfma_f32_16x16x4_f32 (two 16-row halves of the
   // 32-row tile): half the MFMA chain of WN = 1 for stages of <= 128 32-column workgroups, which
-  // otherwise leave half the CUs idle (td3.hip gemm_wn)
+  // otherwise leave half the CUs idle (stages.hip gemm_wn)
   constexpr int WNS = WN == 0 ? 1 : wn_cols(WN);   // waves per K group
   constexpr int WK = NW / WNS;
   constexpr int NT = 64 * NW;                  // threads
@@ -1562,7 +1562,7 @@ __device__ __forceinline__ void gemm_body(int b, int nprob, int tb1, int tb2, in
       }
     }
   }
-  // a separate layer-0 forward stage of the actor phase (td3.hip W1aT): the workgroups of column
+  // a separate layer-0 forward stage of the actor phase (learner.h Plan::W1aT): the workgroups of column
   // tile nt also write its weight rows' columns [kTCol, kTCol + kTN), transposed, for
   // actor_head_bwd -- row n0 + r by row tile r % mtiles (done by row tile 0 alone, the copy was
   // that workgroup's tail: AF_fwd0 +0.9 us)
@@ -1606,7 +1606,7 @@ __global__ __launch_bounds__(64 * gemm_nw(MODE, WN, PRO), WN == 4 ? 4 : WN == kW
 }
 
 // Two independent GEMM stages in one launch (the unit-gradient critic backward beside the target
-// twin's forward, td3.hip): a uniform branch per workgroup picks the stage; the launch takes the
+// twin's forward, step.hip build_step): a uniform branch per workgroup picks the stage; the launch takes the
 // larger LDS and register footprint of the two bodies.
 // Tile placement: stage 1's tiles take the first 8*ceil(nb1/8) workgroup ids, dealt over the 8
 // XCDs as xcd_tile does (consecutive tiles, which share weight columns, on one XCD); stage 2's
@@ -3540,7 +3540,7 @@ static GemmFn pick_gemm(int mode, int wn, int pro) {
   return nullptr;
 }
 
-// The stage pairs the planner merges (td3.hip): {forward layer of the target twin} x {input-grad
+// The stage pairs the planner merges (stages.hip merge_gemm_pair): {forward layer of the target twin} x {input-grad
 // stage of the unit critic backward} at the widths gemm_wn picks for B = 64..1024.
 #define TD3_GEMM2_PAIRS(X)                                            \
   X(0, 1, kProL0, 1, 1, kProCopy) X(0, 0, kProLN, 1, 1, kProLNBwd)     \
@@ -3954,6 +3954,31 @@ int launch_w4_pack(const W4PackArgs& a, hipStream_t s) {
   const int64_t n = (int64_t)a.npair * a.first[a.nmat];
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(w4_pack_kernel, dim3(blocks), dim3(256), 0, s, a);
+  TD3_HIP(hipGetLastError());
+  return 0;
+}
+
+__global__ void pack_kernel(const float* __restrict__ src, int cols, int B, int Bp, float* d1, int ld1,
+                            int c1, float* d2, int ld2, int c2, float* d3, int ld3, int c3) {
+  const int row = blockIdx.x;
+  for (int c = threadIdx.x; c < cols; c += blockDim.x) {
+    const float v = row < B ? src[(size_t)row * cols + c] : 0.f;
+    if (d1) d1[(size_t)row * ld1 + c1 + c] = v;
+    if (d2) d2[(size_t)row * ld2 + c2 + c] = v;
+    if (d3) d3[(size_t)row * ld3 + c3 + c] = v;
+  }
+  (void)Bp;
+}
+
+int launch_pack(const float* src, int cols, int B, int Bp, std::initializer_list<PackDst> dst, hipStream_t s) {
+  if (dst.size() < 1 || dst.size() > 3) {
+    set_error("launch_pack: %zu destinations", dst.size());
+    return -1;
+  }
+  PackDst d[3] = {};
+  for (size_t k = 0; k < dst.size(); ++k) d[k] = dst.begin()[k];
+  hipLaunchKernelGGL(pack_kernel, dim3(Bp), dim3(64), 0, s, src, cols, B, Bp, d[0].p, d[0].ld, d[0].col, d[1].p,
+                     d[1].ld, d[1].col, d[2].p, d[2].ld, d[2].col);
   TD3_HIP(hipGetLastError());
   return 0;
 }

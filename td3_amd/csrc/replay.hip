@@ -42,7 +42,7 @@ namespace td3 {
 // stored as float4 -- four LDS dwords per lane, whatever the record offset, into one 16-B
 // global store -- and its tail / unaligned segments as dwords.  Rows B..Bp-1 are
 // zero-filled so padded batch rows stay finite and contribute nothing downstream.
-// Bytes moved per live row: rec*4 read + sum(len)*4 written (td3.hip input_from_ring).
+// Bytes moved per live row: rec*4 read + sum(len)*4 written (step.hip input_from_ring).
 __device__ __forceinline__ int64_t gather_row_index(const GatherArgs& a, int row) {
   if (a.inject_idx) return a.inject_idx[row];
   const uint64_t size = (uint64_t)*a.d_size;  // issued alongside the counter load

@@ -270,7 +270,7 @@ def test_local_replicas_free_running_philox():
 
 def test_local_replica_queries_after_policy_steps():
     """Replica k > 0 of a local group steps on replica 0's stream: its policy steps record an event
-    there (td3.hip note_actor_update) that its queries wait for.  Queries right after each step,
+    there (step.hip note_actor_update) that its queries wait for.  Queries right after each step,
     without syncs, equal across replicas (lock-step actors) and equal the query after a device sync."""
     from td3_amd.data_parallel import train_local
     S = featured_setup("hc_layer")

@@ -2,7 +2,7 @@
 
 * ragged batches: B = 1, 33, 257 (row tiles of 32 with 31 / 31 / 31 padding rows), and the
   64x64 dW tiles of B >= 512: B = 544 (Bp % 64 = 32: one tile per workgroup, the register-staged
-  dw64_kernel) and B = 640 (Bp % 64 = 0: the split-K persistent dwsk_kernel + its combine, td3.hip
+  dw64_kernel) and B = 640 (Bp % 64 = 0: the split-K persistent dwsk_kernel + its combine, stages.hip
   TD3_DWSK / add_dw_stage; edge tiles with dead quadrants) -- the C_dw stage's kernel is asserted;
 * hidden widths other than the reference's (500, 400, 300) / (500, 400, 200): narrow, odd and
   the 512-wide maximum (every Linear / LayerNorm is padded to 32 in HBM, td3.hip);

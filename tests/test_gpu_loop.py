@@ -53,7 +53,7 @@ def test_select_action_sees_the_actor_update():
 
 def test_select_action_after_steps_on_a_caller_stream():
     """Steps queued on a caller's stream (td3_train_step's `stream` argument): a query after a policy
-    step there waits for it through an event recorded on that stream (td3.hip note_actor_update), a
+    step there waits for it through an event recorded on that stream (step.hip note_actor_update), a
     query after a critic-only step does not wait; both read exactly the sequential actor."""
     import ctypes as C
     import torch

@@ -217,7 +217,7 @@ def test_query_kernel_timeout_fails_loudly_and_recovers():
 @pytest.mark.parametrize("name", ["hc_layer", "hc_none", "hc_wn"])
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 300])
 def test_select_action_eval_q_batch_paths(name, n):
-    """The query paths of td3.hip: n <= 4 rows on the gemv chain (gemv_kernel<1, 2, 4>), up to 256
+    """The query paths of act.hip: n <= 4 rows on the gemv chain (gemv_kernel<1, 2, 4>), up to 256
     padded rows on the GEMM stages with mapped host I/O, more on device buffers and DMA copies
     (kMappedRows) -- actions and both Q values against the oracle row by row; two calls in a
     row reuse the plan's buffers."""
@@ -305,7 +305,7 @@ def test_philox_graph_path_teacher_forced(name):
     """The production path (Philox draws, gather captured in the step graph): the rows and
     noise it drew are read back, the oracle replays the same step, and the results agree.
     HalfCheetah records are sampled inside the first layer (kProGather); Humanoid's 3 KB
-    records by the separate gather kernel (td3.hip Plan::fuse_gather)."""
+    records by the separate gather kernel (learner.h Plan::fuse_gather)."""
     S = featured_setup(name)
     pol, rb = _make(S)
     L = orc.Learner(S["actor"], S["critic"], **S["kw"])
@@ -373,7 +373,7 @@ def test_allreduce_path_single_rank(name, shard, monkeypatch):
 
 
 def test_overlapped_allreduce_schedule_single_rank(monkeypatch):
-    """The overlapped data-parallel schedule (td3.hip add_dw_stage buckets: per-network split-K dW;
+    """The overlapped data-parallel schedule (stages.hip add_dw_stage buckets: per-network split-K dW;
     bucket 0's all-reduce and Adam on the comm stream behind dW_1, bucket 1's on the step stream,
     joined back before the next stage) through RCCL at nranks = 1 (TD3_DP_BUCKETS=2 turns it on without peers):
     Humanoid widths at B = 1024, a critic-only and a policy step against the oracle, both Adam moments
@@ -434,7 +434,7 @@ def test_layer0_widths_teacher_forced(sd, ad):
 @pytest.mark.parametrize("B", [512, 1024])
 def test_large_batch_teacher_forced(B):
     """Batches >= 512 switch the wide stages to 128-column GEMM workgroups with the K chunks
-    streamed (td3.hip gemm_wn): a critic-only and an actor step against the oracle."""
+    streamed (stages.hip gemm_wn): a critic-only and an actor step against the oracle."""
     S = featured_setup("hc_layer")
     S["B"] = B
     pol, rb = _make(S)

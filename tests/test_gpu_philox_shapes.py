@@ -1,5 +1,5 @@
 """The production first layer (Philox rows drawn and read from the ring inside the first forward
-launch, td3.hip Plan::body_ring) against the oracle at the shapes where its kernels change.
+launch, learner.h Plan::body_ring) against the oracle at the shapes where its kernels change.
 
 Every case runs a critic-only and a policy step from the oracle's state with NO injected indices:
 the rows and the noise the step drew are read back, the batch is taken from the host-side
@@ -15,7 +15,7 @@ learner then runs the same step from the same state with those indices and that 
 3 = kProGather, 5 = kProL0G).
 
 First-layer instantiations of the ring-sampled step (kernels.hip) and the cases that run them.
-The planner (td3.hip gemm_wn, can_fuse_l0, l0r16_config) picks per phase: a policy step has a
+The planner (stages.hip gemm_wn, can_fuse_l0, l0r16_config) picks per phase: a policy step has a
 fourth network (the online actor) in the launch, so hc_none / hc_wn / inj_noise (B = 256) run
 l0r16 on the critic-only step and the 32-row GEMM on the policy step.
 

@@ -1,4 +1,4 @@
-"""The k-quad weight images (td3.hip Group::P4 / T4, kernels.h GemmProb::wsk) change where the
+"""The k-quad weight images (learner.h Group::P4 / T4, kernels.h GemmProb::wsk) change where the
 forward GEMM stages read their weights, not what they read or the order they sum it in: a plan that
 reads the images (TD3_W4=1, the default) and one that reads the row-major arena
 (TD3_W4=0) give bit-identical parameters -- through Philox steps, a td3_set_params mid-run (the

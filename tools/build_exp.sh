@@ -22,7 +22,9 @@ if [[ "$flags" == *TD3_KO_* || "$flags" == *TD3_X_* || "$flags" == *TD3_STORE_PO
   if [[ "$flags" == *TD3_KO_* || "$flags" == *TD3_X_* ]]; then patch -s "$src/kernels.hip" tools/exp_patches/knockout.patch; fi
   if [[ "$flags" == *STORE* ]]; then patch -s "$src/dev.h" tools/exp_patches/store_policy.patch; fi
 fi
+# the product's own source list (td3_amd/build.py SOURCES: csrc/NAME.hip), taken from $src
+sources=$(python3 -c 'from td3_amd.build import SOURCES; print(" ".join(SOURCES))')
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -shared -ffp-contract=off -mllvm -amdgpu-kernarg-preload-count=6 $flags \
-  $src/replay.hip $src/kernels.hip $src/encoder.hip $src/td3.hip \
+  $(for f in $sources; do echo "$src/${f#csrc/}"; done) \
   -o $out/libtd3hip_$name.so -lrccl
 ls -la $out/libtd3hip_$name.so

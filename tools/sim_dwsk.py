@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Model of the split-K dW unit assignment (td3.hip make_dw_split) at Humanoid C_dw, B = 1024: per
+"""Model of the split-K dW unit assignment (stages.hip make_dw_split) at Humanoid C_dw, B = 1024: per
 XCD, how long each 64-row block of a dZ / U panel stays live in L2 between its first and last
 reader, for the tile-major walk (dwsk_kernel) and the step-major walk (dwsk_sm_kernel).  CPU only."""
 # simulate dwsk unit assignment for Humanoid critic C_dw (B=1024): row-step skew within an XCD
