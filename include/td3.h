@@ -31,9 +31,10 @@
  *                        n-step returns on device rows (no counterpart in the reference): each tick's
  *                        rows are stored and the previous n-1 ticks' rows mature in the ring, in one launch
  *   rb_enable_priorities / rb_set_priorities / rb_update_priorities / rb_sample_prioritized /
- *   td3_train_step_prioritized
+ *   td3_train_step_prioritized / td3_train_step_prioritized_particles
  *                        prioritized experience replay on the device ring (no counterpart in the
  *                        reference): a 64-ary sum tree next to the ring, the weighted critic loss
+ *                        of either learner
  *   rs_create / rs_tick / rs_get_state / rs_set_state / rs_read_episodes / rs_info
  *                        rollout statistics of a GPU-resident vector environment (no counterpart in the
  *                        reference): running observation / reward normalisation and the episode log,
@@ -463,9 +464,9 @@ int td3_train_step(td3_handle* h, rb_handle* rb, int batch, void* stream,
  * td3_train_step; stats->idx receives the rows drawn, stats->critic_loss the weighted loss; per
  * (nullable) the weights and td_abs of the step.  Every other step entry point keeps unit weights: the
  * first of them after a prioritized step refills the weight buffer on its own stream before its body.
- * Returns -1 with a message for: a particle learner; a handle in a td3_comm_init or
- * td3_comm_init_local group; a ring without priorities; a ring whose kind or dims do not match; beta
- * outside [0, 1]; an empty ring. */
+ * Returns -1 with a message for: a particle learner (its step is td3_train_step_prioritized_particles
+ * below); a handle in a td3_comm_init or td3_comm_init_local group; a ring without priorities; a ring
+ * whose kind or dims do not match; beta outside [0, 1]; an empty ring. */
 typedef struct td3_per_stats {
   float* weight;           /* nullable host [B]: importance weights used */
   float* td_abs;           /* nullable host [B]: the |TD error| written back */
@@ -473,6 +474,26 @@ typedef struct td3_per_stats {
 int td3_train_step_prioritized(td3_handle* h, rb_handle* rb, int batch, double beta, void* stream,
                                const float* inject_u, const float* inject_noise, td3_step_stats* stats,
                                td3_per_stats* per);
+/* The same step for a particle learner (TD3_particles) on a prioritized particle ring, one device.
+ * With B rows, A = action_dim Q outputs per row, J online critics (2 with CDQ, 1 without) and w_r the
+ * importance weight of row r (one per transition, shared by its A outputs): y as td3_train_step;
+ * critic loss sum_j 1/(B*A) sum_r w_r sum_o (Q_j,r,o - y_r,o)^2, i.e.
+ * dL/dQ_j,r,o = 2/(B*A) w_r (Q_j,r,o - y_r,o) -- the actor loss is not weighted;
+ * td_abs_r = 1/(J*A) sum_j sum_o |Q_j,r,o - y_r,o| in float32, each critic's sum over o in increasing
+ * order, the critics added in order j (A = 1 with CDQ: the featured step's 0.5f * (|Q1 - y| + |Q2 - y|)).
+ * Everything else is td3_train_step_prioritized's contract: one read section of the ring around the
+ * draw (into the step's index and weight buffers), the gather of those rows' small fields (the encoders
+ * read their particle blocks in the ring), the body and rb_update_priorities(rows, td_abs), where a row
+ * drawn twice keeps its larger value; inject_u / inject_noise / stats / per as there
+ * (stats->critic_loss the weighted loss, stats->y / q1 / q2 [B][A]); no host synchronisation unless one
+ * of those forces it.  Every other particle step entry point (td3_train_step,
+ * td3_train_step_batch_particles, td3_actor_learn_particles) keeps unit weights.
+ * Returns -1 with a message, before any GPU work, for: a featured learner; a handle in a td3_comm_init
+ * or td3_comm_init_local group; a ring without priorities; a ring whose kind or dims do not match; beta
+ * outside [0, 1]; an empty ring. */
+int td3_train_step_prioritized_particles(td3_handle* h, rb_handle* rb, int batch, double beta, void* stream,
+                                         const float* inject_u, const float* inject_noise,
+                                         td3_step_stats* stats, td3_per_stats* per);
 /* Same step on an already-sampled batch (device float32 pointers, contiguous). */
 int td3_train_step_batch(td3_handle* h, const float* state, const float* action,
                          const float* next_state, const float* reward, const float* not_done,
@@ -610,6 +631,13 @@ int td3_debug_activation(td3_handle* h, int eval, int layer, float* out, int row
  * bit 1 = the plan's optimizer steps are sharded over ranks.  A rebuild that leaves a sharded schedule
  * gathers the Adam moments first (collective on RCCL ranks, as td3_dp_gather_optimizer_state). */
 int td3_debug_plan_flags(const td3_handle* h, int* flags);
+/* Measurement instrumentation (tools/bench_per.py): queue on `stream` one stage of the last prioritized
+ * step of this handle on this ring, over the rows that step drew (the plan's buffers still hold them):
+ * stage 0 the gather of those rows into the batch buffers, inside a read section of its own; stage 1 the
+ * particle step's combine of the critics' |TD error| rows (a featured step has none: -1).  -1 before the
+ * first prioritized step of the current plan on this ring.  The draw and the priority update are
+ * rb_sample_prioritized and rb_update_priorities themselves. */
+int td3_debug_per_stage(td3_handle* h, rb_handle* rb, int stage, void* stream);
 
 /* Test seam of the one-launch query's failure path: in the next n select_action / eval_q launches
  * (existing query plans) workgroup 0 acts as if its in-launch layer-1 poll had timed out.  The query

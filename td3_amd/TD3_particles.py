@@ -81,8 +81,10 @@ class TD3(_FeaturedTD3):
     """TD3_particles.TD3 (TD3_particles.py:135-224) on the HIP pipeline."""
 
     def __init__(self, obs_space, action_space, lr=1e-4, norm=None, CDQ=True, device=None, seed=0,
-                 use_graph="auto", init="torch", **kwargs):
+                 use_graph="auto", init="torch", per_beta=None, **kwargs):
         TD3_base.__init__(self, **kwargs)
+        # the importance-weight exponent of prioritized steps; None: prioritized rings are refused
+        self.per_beta = per_beta
         self._lib = _lib.load()
         if norm not in (None, "layer"):
             raise ValueError(f"norm={norm!r} is not supported (None or 'layer')")
@@ -242,12 +244,20 @@ class TD3(_FeaturedTD3):
                   "td3_actor_learn_particles")
         return float(loss.value) if stats else None
 
-    def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False):
-        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back."""
-        if getattr(replay_buffer, "prioritized", False):
-            raise NotImplementedError("TD3_particles.TD3.train on a prioritized ring: the particle learner's "
-                                      "critic loss takes no importance weights (prioritized steps are "
-                                      "TD3_featured only); train on a ring without enable_priorities")
+    def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False, u=None):
+        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back.  With
+        ``per_beta`` set, on a prioritized ring (``enable_priorities``) without ``indices`` the step draws
+        its rows by priority, weights the critic loss (one weight per transition, shared by its Q
+        outputs) and writes the new priorities back, all on the device; ``u`` (``[batch_size]`` mass
+        fractions) replaces that draw and the stats gain ``"weight"`` and ``"td_abs"``."""
+        on_pri_ring = getattr(replay_buffer, "prioritized", False)
+        if on_pri_ring and self.per_beta is None:
+            raise NotImplementedError("TD3_particles.TD3.train on a prioritized ring: set per_beta (a float in "
+                                      "[0, 1], e.g. TD3(..., per_beta=0.4)) to take prioritized steps, or "
+                                      "train on a ring without enable_priorities")
+        prioritized = on_pri_ring and indices is None and isinstance(replay_buffer, ReplayBuffer_particles)
+        if u is not None and not prioritized:
+            raise ValueError("u is the draw of a prioritized step: enable_priorities on the ring, no indices")
         B, A = int(batch_size), self.action_dim
         st = None
         keep = []
@@ -259,7 +269,22 @@ class TD3(_FeaturedTD3):
         nz = None
         if noise is not None:
             nz = np.ascontiguousarray(np.asarray(noise, dtype=np.float32).reshape(B, A))
-        if isinstance(replay_buffer, ReplayBuffer_particles):
+        if prioritized:
+            replay_buffer.flush(self._lib.td3_stream(self._h))   # in the step's stream order
+            per = None
+            if stats:
+                per = _lib.td3_per_stats()
+                weight, td_abs = np.empty(B, np.float32), np.empty(B, np.float32)
+                per.weight, per.td_abs = weight.ctypes.data, td_abs.ctypes.data
+            uu = None
+            if u is not None:
+                uu = np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(B))
+            check(self._lib.td3_train_step_prioritized_particles(
+                self._h, replay_buffer.handle, B, float(self.per_beta), self._stream(),
+                _lib.fptr(uu) if uu is not None else None, _lib.fptr(nz) if nz is not None else None,
+                C.byref(st) if st is not None else None, C.byref(per) if per is not None else None),
+                "td3_train_step_prioritized_particles")
+        elif isinstance(replay_buffer, ReplayBuffer_particles):
             replay_buffer.flush(self._lib.td3_stream(self._h))   # in the step's stream order
             ix = None
             if indices is not None:
@@ -289,4 +314,6 @@ class TD3(_FeaturedTD3):
                "y": keep[0], "q1": keep[1], "q2": keep[2], "idx": keep[3], "noise": keep[4]}
         if st.actor_step:
             out["actor_loss"] = st.actor_loss
+        if prioritized:
+            out["weight"], out["td_abs"] = weight, td_abs
         return out

@@ -152,6 +152,8 @@ SIGNATURES = {
     "td3_train_step": (C.c_int, [_P, _P, C.c_int, _P, _I64, _F, C.POINTER(td3_step_stats)]),
     "td3_train_step_prioritized": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, _F, _F,
                                              C.POINTER(td3_step_stats), C.POINTER(td3_per_stats)]),
+    "td3_train_step_prioritized_particles": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, _F, _F,
+                                                       C.POINTER(td3_step_stats), C.POINTER(td3_per_stats)]),
     "td3_train_step_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _F,
                                        C.POINTER(td3_step_stats)]),
     "td3_select_action": (C.c_int, [_P, _F, _F, C.c_int]),
@@ -182,6 +184,7 @@ SIGNATURES = {
     "td3_stage_bytes": (C.c_double, [_P, C.c_int]),
     "td3_debug_activation": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "td3_debug_plan_flags": (C.c_int, [_P, _P]),
+    "td3_debug_per_stage": (C.c_int, [_P, _P, C.c_int, _P]),
     "td3_debug_act_fail": (C.c_int, [_P, C.c_int]),
     "td3_last_error": (C.c_char_p, []),
 }

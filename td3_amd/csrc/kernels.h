@@ -236,17 +236,18 @@ enum : int {
   kH3 = 0,       // x3
   kGamma3 = 3,   // x3
   kBeta3 = 6,    // x3
-  kW4 = 9,       // x3: [nq][ldw4]
-  kB4 = 12,      // x3
-  kReward = 15,
+  kW4 = 9,       // x3: [nq][ldw4]; the head's bias sits in the same arena, kB4Off floats behind it
+  kReward = 12,
   kNotDone,
   kDZ4,          // out: dZ4_j (ld 32)
   kDU3,          // out: dU3_j
   kU3,           // out: LN3 output rows of Q_j
   kStats3,       // out: LN3 (mean, rstd) of Q_j
   kY,            // out: target [Bp][32] (written by j = 0)
-  kSqErr,        // out: squared errors of Q_j, summed over the outputs [Bp]
+  kSqErr,        // out: weighted squared errors of Q_j, summed over the outputs [Bp]
   kQ,            // out: Q_j [Bp][32]
+  kW,            // importance weight of the row [Bp] (ones unless the step is prioritized)
+  kTd,           // out: sum over the outputs of |Q_j - y| of a live row, 0 for a pad row [Bp]
   kNumPtr
 };
 enum : int {
@@ -256,7 +257,8 @@ enum : int {
   kNq,           // Q outputs per row
   kLdw4,
   kCdq,          // clipped double-Q on
-  kNumInt
+  kB4Off,        // x3: head bias = kW4 + n's pointer + this many floats
+  kNumInt = kB4Off + 3
 };
 enum : int {
   kDiscount = 0,

@@ -846,6 +846,10 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
 // The Q networks of TD3_particles output one value per action dimension (Q head [A, 300],
 // TD3_particles.py:91); y = r + not_done*discount*min(Q1', Q2') broadcasts over them (:183-189)
 // and F.mse_loss averages over B*A.  Values / targets are kept as [Bp][32] rows.
+// Each squared error carries its row's importance weight w (one per transition, shared by its A
+// outputs; 1 unless the step is prioritized, and then exact): dL/dQ_j,r,o = 2/(B*A) w_r (Q_j,r,o - y_r,o).
+// Each critic's problem also leaves its rows' sum over o of |Q_j - y| (kTd): the prioritized step
+// combines the critics' rows into the |TD error| it writes back (per_td_combine_kernel, step.hip).
 
 // (operands: critic_loss_p, kernels.h)
 template <bool NORM>
@@ -865,6 +869,7 @@ __device__ __forceinline__ void row_critic_loss_p(const GemmProb& P, const RowCt
     }
   }
   const float rw = gld(P.ex[kReward] + c.row), nd = gld(P.ex[kNotDone] + c.row);
+  const float iw = gld(P.ex[kW] + c.row);      // with the row's other loads: one round trip
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) h[0][jj] = xq[0][jj];
   float m0[1], s0[1], m1[1], s1[1], mq[1], sq[1];
@@ -880,19 +885,22 @@ __device__ __forceinline__ void row_critic_loss_p(const GemmProb& P, const RowCt
   float gu[1][8];
 #pragma unroll
   for (int jj = 0; jj < 8; ++jj) gu[0][jj] = 0.f;
-  float se = 0.f;
+  // mse over B*A, times the row's importance weight (1 unless the step is prioritized, and then exact)
+  const float gs = P.exf[kGradScale] * iw;
+  float se = 0.f, ta = 0.f;
   for (int o = 0; o < nq; ++o) {
     float w0[8], w1[8], wq[8];
     rv_load(w0, P.ex[kW4] + (size_t)o * ldw4, ld3, c.lane);
     rv_load(w1, P.ex[kW4 + 1] + (size_t)o * ldw4, ld3, c.lane);
     rv_load(wq, P.ex[kW4 + 2] + (size_t)o * ldw4, ld3, c.lane);
-    const float tq0 = wsum(rv_pdot(x0[0], w0, K3, c.lane)) + gld(P.ex[kB4] + o);
-    const float tq1 = cdq ? wsum(rv_pdot(x1[0], w1, K3, c.lane)) + gld(P.ex[kB4 + 1] + o) : tq0;
-    const float q = wsum(rv_pdot(xq[0], wq, K3, c.lane)) + gld(P.ex[kB4 + 2] + o);
+    const float tq0 = wsum(rv_pdot(x0[0], w0, K3, c.lane)) + gld(P.ex[kW4] + (P.exi[kB4Off] + o));
+    const float tq1 = cdq ? wsum(rv_pdot(x1[0], w1, K3, c.lane)) + gld(P.ex[kW4 + 1] + (P.exi[kB4Off + 1] + o)) : tq0;
+    const float q = wsum(rv_pdot(xq[0], wq, K3, c.lane)) + gld(P.ex[kW4 + 2] + (P.exi[kB4Off + 2] + o));
     const float y = rw + (nd * P.exf[kDiscount]) * fminf(tq0, tq1);          // TD3_particles.py:183-189
     const float d = q - y;
-    const float gq = live ? P.exf[kGradScale] * d : 0.f;                       // mse over B*A
+    const float gq = live ? gs * d : 0.f;
     se += live ? d * d : 0.f;
+    ta += live ? fabsf(d) : 0.f;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) gu[0][jj] += gq * wq[jj];
     if (c.lane == 0) {
@@ -902,7 +910,8 @@ __device__ __forceinline__ void row_critic_loss_p(const GemmProb& P, const RowCt
     }
   }
   if (c.lane == 0) {
-    gst(P.ex[kSqErr] + c.row, se);
+    gst(P.ex[kSqErr] + c.row, iw * se);
+    gst(P.ex[kTd] + c.row, ta);
     if (NORM) {
       gst(P.ex[kStats3] + c.row, mq[0]);
       gst(P.ex[kStats3] + (c.Bp + c.row), sq[0]);

@@ -154,11 +154,15 @@ struct Plan {
   float* W1aT = nullptr;
   int64_t* d_idx = nullptr;
   int64_t* d_inject_idx = nullptr;
-  // featured: the rows' importance weights in the critic loss (target_loss::kW), ones unless the last
-  // step was prioritized (per_w_dirty: the next other step refills them, ensure_unit_weights), the
-  // rows' |TD error| (kTd) and the injected mass fractions of a prioritized draw
+  // the rows' importance weights in the critic loss (target_loss::kW / critic_loss_p::kW), ones unless
+  // the last step was prioritized (per_w_dirty: the next other step refills them, ensure_unit_weights),
+  // the rows' |TD error| and the injected mass fractions of a prioritized draw
   float *per_w = nullptr, *per_td = nullptr, *per_u = nullptr;
   bool per_w_dirty = false;
+  // particles: each critic's rows' sum over the Q outputs of |Q_j - y| (critic_loss_p::kTd), [J][Bp];
+  // the prioritized step combines them into per_td (per_td_combine_kernel)
+  float* per_tdj = nullptr;
+  uint64_t per_ring_gen = 0;            // Ring::gen of the last prioritized step's ring (d_inject_idx holds its rows)
   EvalB TA, Q[2], A, TQ[2], AQ;
   // device problem tables (owned)
   std::vector<void*> tables;
@@ -339,7 +343,7 @@ struct td3_handle {
   // td3_probe_kernel: while set, steps launch directly and every stage launching `probe_kernel` is
   // bracketed by a pair of HIP events on the step's stream (probe_ev[2k], probe_ev[2k + 1])
   bool probing = false;
-  bool per_step = false;                      // inside td3_train_step_prioritized: the body keeps its weights
+  bool per_step = false;                      // inside a prioritized step: the body keeps its weights
   std::string probe_kernel;
   std::vector<hipEvent_t> probe_ev;
   int probe_used = 0;

@@ -449,6 +449,10 @@ static int build_step_particles(td3_handle* h, int B) {
     P->d_idx = (int64_t*)S.take(2 * (size_t)Bp);
     P->d_inject_idx = (int64_t*)S.take(2 * (size_t)Bp);
     P->d_iota = (int64_t*)S.take(2 * (size_t)Bp);
+    P->per_w = S.take(Bp);
+    P->per_td = S.take(Bp);
+    P->per_u = S.take(Bp);
+    P->per_tdj = S.take(2 * (size_t)Bp);
     P->pbatch = S.take((size_t)Bp * 2 * N * D);
     alloc_eval(S, an, Bp, P->XTA, P->ld_a, false, norm, true, P->TA);
     alloc_eval(S, an, Bp, P->XA, P->ld_a, true, norm, true, P->A);
@@ -471,6 +475,8 @@ static int build_step_particles(td3_handle* h, int B) {
     std::vector<int64_t> iota(Bp);
     for (int i = 0; i < Bp; ++i) iota[i] = i;
     TD3_HIP(hipMemcpy(P->d_iota, iota.data(), Bp * 8, hipMemcpyHostToDevice));
+    const std::vector<float> ones((size_t)Bp, 1.0f);
+    TD3_HIP(hipMemcpy(P->per_w, ones.data(), (size_t)Bp * sizeof(float), hipMemcpyHostToDevice));
   }
 
   const float* Pa = h->actor.P;
@@ -584,7 +590,7 @@ static int build_step_particles(td3_handle* h, int B) {
             p.ex[cp::kGamma3 + n] = const_cast<float*>(hp[n] + hn[n]->ln[2].offg);
             p.ex[cp::kBeta3 + n] = const_cast<float*>(hp[n] + hn[n]->ln[2].offb);
             p.ex[cp::kW4 + n] = const_cast<float*>(hp[n] + hn[n]->lin[3].offW);
-            p.ex[cp::kB4 + n] = const_cast<float*>(hp[n] + hn[n]->lin[3].offb);
+            p.exi[cp::kB4Off + n] = (int)(hn[n]->lin[3].offb - hn[n]->lin[3].offW);   // one arena
           }
           p.ex[cp::kReward] = P->R;
           p.ex[cp::kNotDone] = P->ND;
@@ -595,6 +601,8 @@ static int build_step_particles(td3_handle* h, int B) {
           p.ex[cp::kY] = P->Y;
           p.ex[cp::kSqErr] = P->sqerr + (size_t)j * Bp;
           p.ex[cp::kQ] = P->Q[j].Qv;
+          p.ex[cp::kW] = P->per_w;
+          p.ex[cp::kTd] = P->per_tdj + (size_t)j * Bp;
           p.Aout = P->Q[j].GZ[2];
           p.ldao = qj.lin[2].Np;
           p.exi[cp::kK3] = qj.lin[2].N;
@@ -750,6 +758,25 @@ int ensure_unit_weights(td3_handle* h, hipStream_t s) {
   hipLaunchKernelGGL(fill_f32_kernel, dim3((P->Bp + 255) / 256), dim3(256), 0, s, P->per_w, P->Bp, 1.0f);
   TD3_HIP(hipGetLastError());
   P->per_w_dirty = false;
+  return 0;
+}
+
+// The particle learner's |TD error| of a row: its J critics' sums over the A outputs of |Q_j - y|
+// (critic_loss_p::kTd, one [Bp] row per critic), added in critic order and scaled by 1/(J*A).  One
+// fixed-order add per row; pad rows hold 0.
+__global__ void per_td_combine_kernel(const float* tdj, int nj, int Bp, float scale, float* td) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp) return;
+  float a = tdj[i];
+  for (int j = 1; j < nj; ++j) a += tdj[(size_t)j * Bp + i];
+  td[i] = a * scale;
+}
+
+static int combine_td(const td3_handle* h, const Plan* P, hipStream_t s) {
+  const int nj = h->cdq ? 2 : 1;
+  hipLaunchKernelGGL(per_td_combine_kernel, dim3((P->Bp + 255) / 256), dim3(256), 0, s, P->per_tdj, nj, P->Bp,
+                     1.0f / (float)(nj * h->ad), P->per_td);
+  TD3_HIP(hipGetLastError());
   return 0;
 }
 
@@ -968,14 +995,11 @@ int td3_train_step(td3_handle* h, rb_handle* rbh, int batch, void* stream, const
   return finish_step(h, actor_phase, s, stats);
 }
 
-int td3_train_step_prioritized(td3_handle* h, rb_handle* rbh, int batch, double beta, void* stream,
-                               const float* inject_u, const float* inject_noise, td3_step_stats* stats,
-                               td3_per_stats* per) {
-  TD3_ARG(h && rbh, "null handle");
-  TD3_ARG(batch > 0, "batch must be positive");
-  TD3_ARG(beta >= 0.0 && beta <= 1.0, "beta must be in [0, 1]");
-  TD3_ARG(!h->particles, "td3_train_step_prioritized on a particle learner (its loss takes no importance weights)");
-  TD3_ARG(!h->comm && !h->local, "td3_train_step_prioritized on a data-parallel handle (comm group attached)");
+// The prioritized step of either learner kind, after the kind check of its entry point.
+static int prioritized_step(td3_handle* h, rb_handle* rbh, int batch, double beta, void* stream,
+                            const float* inject_u, const float* inject_noise, td3_step_stats* stats,
+                            td3_per_stats* per, const char* dp_msg) {
+  TD3_ARG(!h->comm && !h->local, dp_msg);
   Ring* r = reinterpret_cast<Ring*>(rbh);
   TD3_RC(check_ring(h, r, kLearnerStep));
   TD3_ARG(r->pri.on, "priorities are not enabled on this ring (rb_enable_priorities)");
@@ -991,12 +1015,14 @@ int td3_train_step_prioritized(td3_handle* h, rb_handle* rbh, int batch, double 
     TD3_HIP(hipMemcpyAsync(P->noise, inject_noise, (size_t)batch * h->ad * 4, hipMemcpyHostToDevice, s));
   const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
   P->per_w_dirty = true;
+  P->per_ring_gen = r->gen;
   TD3_RC(ring_draw_prioritized(r, batch, beta, inject_u ? P->per_u : nullptr, P->d_inject_idx, P->d_idx, P->per_w, s));
   TD3_RC(input_from_ring(h, r, P, true, s));
   h->per_step = true;
   const int rc = run_body(h, actor_phase, inject_noise ? 1 : 0, s, nullptr);
   h->per_step = false;
   TD3_RC(rc);
+  if (P->particles) TD3_RC(combine_td(h, P, s));   // (the featured loss row writes the row's |TD error| itself)
   TD3_RC(ring_store_priorities(r, P->d_inject_idx, P->per_td, batch, true, s));
   TD3_RC(ring_end_read(r, s));                   // later adds wait for the step and its write-back
   if (inject_u || inject_noise) TD3_HIP(hipStreamSynchronize(s));   // host sources are pageable
@@ -1007,6 +1033,44 @@ int td3_train_step_prioritized(td3_handle* h, rb_handle* rbh, int batch, double 
     if (per->td_abs) TD3_HIP(hipMemcpy(per->td_abs, P->per_td, (size_t)batch * 4, hipMemcpyDeviceToHost));
   }
   return 0;
+}
+
+int td3_debug_per_stage(td3_handle* h, rb_handle* rbh, int stage, void* stream) {
+  TD3_ARG(h && rbh, "null handle");
+  TD3_ARG(stage == 0 || stage == 1, "stage 0 (gather) or 1 (combine)");
+  Ring* r = reinterpret_cast<Ring*>(rbh);
+  Plan* P = h->plan.get();
+  TD3_ARG(P && P->per_ring_gen != 0 && ring_alive(r, P->per_ring_gen),
+          "run a prioritized step on this ring first (the plan's buffers hold its rows)");
+  TD3_ARG(stage == 0 || P->particles, "the featured step has no combine (its loss row writes the |TD error|)");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  if (stage == 1) return combine_td(h, P, s);
+  TD3_RC(ring_begin_read(r, s));
+  TD3_RC(input_from_ring(h, r, P, true, s));
+  return ring_end_read(r, s);
+}
+
+int td3_train_step_prioritized(td3_handle* h, rb_handle* rbh, int batch, double beta, void* stream,
+                               const float* inject_u, const float* inject_noise, td3_step_stats* stats,
+                               td3_per_stats* per) {
+  TD3_ARG(h && rbh, "null handle");
+  TD3_ARG(batch > 0, "batch must be positive");
+  TD3_ARG(beta >= 0.0 && beta <= 1.0, "beta must be in [0, 1]");
+  TD3_ARG(!h->particles, "td3_train_step_prioritized on a particle learner (use td3_train_step_prioritized_particles)");
+  return prioritized_step(h, rbh, batch, beta, stream, inject_u, inject_noise, stats, per,
+                          "td3_train_step_prioritized on a data-parallel handle (comm group attached)");
+}
+
+int td3_train_step_prioritized_particles(td3_handle* h, rb_handle* rbh, int batch, double beta, void* stream,
+                                         const float* inject_u, const float* inject_noise,
+                                         td3_step_stats* stats, td3_per_stats* per) {
+  TD3_ARG(h && rbh, "null handle");
+  TD3_ARG(batch > 0, "batch must be positive");
+  TD3_ARG(beta >= 0.0 && beta <= 1.0, "beta must be in [0, 1]");
+  TD3_ARG(h->particles, "td3_train_step_prioritized_particles on a featured learner (use td3_train_step_prioritized)");
+  return prioritized_step(h, rbh, batch, beta, stream, inject_u, inject_noise, stats, per,
+                          "td3_train_step_prioritized_particles on a data-parallel handle (comm group attached)");
 }
 
 int td3_train_step_batch(td3_handle* h, const float* state, const float* action, const float* next_state,
