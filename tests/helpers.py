@@ -50,15 +50,54 @@ def particle_setup(name):
     return particle_setup_dims(Fd, N, D, A, norm, cdq, B, steps)
 
 
-def particle_setup_dims(Fd, N, D, A, norm="layer", cdq=True, B=32, steps=2):
+def particle_setup_dims(Fd, N, D, A, norm="layer", cdq=True, B=32, steps=2, rows=gen.BUFFER_ROWS, data=None):
+    """A particle setup of any shape (no golden fixture: oracle-only parity).  ``data`` (the seven
+    arrays of ``gen.fill_particle_buffer``, ``rows`` of them) replaces the default ring rows; it is
+    returned as ``S["data"]`` for the GPU ring (``test_gpu_particles._make(S, rows, data)``)."""
     a0 = gen.init_params(gen.particle_actor_shapes(Fd, D, A, norm), gen.SEED)
     c0 = gen.init_params(gen.particle_critic_shapes(Fd, D, A, norm, cdq), gen.SEED + 100)
-    buf = orc.ParticleBuffer(Fd, N, D, A, gen.BUFFER_ROWS)
-    f, p, a, f2, p2, r, d = gen.fill_particle_buffer(Fd, N, D, A, gen.BUFFER_ROWS, gen.SEED)
-    for i in range(gen.BUFFER_ROWS):
+    buf = orc.ParticleBuffer(Fd, N, D, A, rows)
+    if data is None:
+        data = gen.fill_particle_buffer(Fd, N, D, A, rows, gen.SEED)
+    f, p, a, f2, p2, r, d = data
+    for i in range(rows):
         buf.add((f[i], p[i]), a[i], (f2[i], p2[i]), r[i], d[i])
     return dict(F=Fd, N=N, D=D, A=A, norm=norm, cdq=cdq, B=B, steps=steps, actor=a0,
-                critic=c0, buf=buf, kw=dict(norm=norm, cdq=cdq))
+                critic=c0, buf=buf, kw=dict(norm=norm, cdq=cdq), rows=rows, data=data)
+
+
+# The dyadic grid of tests/test_gpu_particle_edges.py: with particles on multiples of 1/8 in [-1, 1]
+# and the encoder parameters below, every conv1 pre-activation is an odd multiple of 1/256
+# (|z1| <= 8.5 at D <= 16) and every conv2 pre-activation an odd multiple of 1/8192 (|z2| < 545):
+# every partial sum, in any order, is exact in fp32 (< 2^23 units) and no pre-activation is zero,
+# so two correct fp32 implementations take the same relu' decisions in the encoder.
+GRID_Z1_UNIT, GRID_Z2_UNIT = 1.0 / 256, 1.0 / 8192
+
+
+def grid_particles(x):
+    """Particle coordinates on multiples of 1/8 in [-1, 1]."""
+    return np.round(np.clip(np.asarray(x, np.float64), -1.0, 1.0) * 8.0) / 8.0
+
+
+def particle_grid_params(P, seed):
+    """A copy of state dict ``P`` with every encoder's parameters redrawn on the dyadic grid:
+    conv1.weight multiples of 1/16 in [-1/2, 1/2], conv1.bias odd multiples of 1/256 in (-1/2, 1/2),
+    conv2.weight multiples of 1/16 in [-1/4, 1/4], conv2.bias odd multiples of 1/8192 in (-1/4, 1/4)."""
+    rs = np.random.RandomState(seed)
+    out = {k: v.copy() for k, v in P.items()}
+    for k, v in out.items():
+        if k.endswith("conv1.weight"):
+            g = rs.randint(-8, 9, size=v.shape) / 16.0
+        elif k.endswith("conv1.bias"):
+            g = (2 * rs.randint(-64, 64, size=v.shape) + 1) / 256.0
+        elif k.endswith("conv2.weight"):
+            g = rs.randint(-4, 5, size=v.shape) / 16.0
+        elif k.endswith("conv2.bias"):
+            g = (2 * rs.randint(-1024, 1024, size=v.shape) + 1) / 8192.0
+        else:
+            continue
+        out[k] = g.astype(np.float32)
+    return out
 
 
 def summary_close(arr, stats, samples, salt, rtol, atol, what=""):

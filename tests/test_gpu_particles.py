@@ -2,7 +2,12 @@
 
 Same tolerances as tests/test_gpu_parity.py.  The golden fixtures hold
 F=7, N=16, D=9, A=3, B=32 (one particle tile); ``test_many_particle_tiles`` runs N=350
-(11 tiles, the last one masked) against the oracle directly.
+(11 tiles, the last one masked) against the oracle directly.  Every other particle shape is in
+tests/test_gpu_particle_edges.py: all four DK instantiations of the encoder kernels (D = 1, 4, 5, 8,
+12, 13, 16), N = 1, 31, 32, 33, 65, B = 1, 33, 130, 257 (ragged batches, uneven enc_bwd_kernel row
+ranges), A = 1, F = 1, the 512-column input (F = 352, A = 32) and norm=None without CDQ at an edge,
+with the encoder gradients through both Adam moments; tests/test_gpu_gradients.py has them at the
+golden shape, tests/test_gpu_c4_fullsize.py runs N = 350 at B = 4096.
 """
 import numpy as np
 import pytest
