@@ -39,6 +39,9 @@
  *                        rollout statistics of a GPU-resident vector environment (no counterpart in the
  *                        reference): running observation / reward normalisation and the episode log,
  *                        one launch per tick
+ *   td3_log_enable / td3_log_info / td3_log_read / td3_log_set
+ *                        the training log (no counterpart in the reference): per-step losses and Q
+ *                        statistics of either learner in a device ring, one opt-in launch per logged step
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -564,6 +567,92 @@ int td3_select_action_particles_device(td3_handle* h, const float* feat, const f
 int td3_eval_q_particles_device(td3_handle* h, const float* feat, const float* part, const float* action,
                                 int n, float* q_out, void* stream);
 
+/* ------------------------------------------------------------------ training log */
+/* Per-step losses and Q statistics of the learner, kept on the device (no counterpart in the reference;
+ * what a host loop would print from the loss tensors of TD3.train).  td3_step_stats reports them too, but
+ * stops the queue on every step; the log is a ring of `capacity` td3_log_entry in device memory, written
+ * by ONE extra launch per logged step (train_log_kernel: one workgroup of 256 threads) and read when the
+ * caller chooses.  A learner without the log queues nothing new: its steps stay bit for bit what they are.
+ * The log belongs to the handle, not to the step plan: a rebuild at another batch size keeps it, and every
+ * entry records its own `batch`.
+ *
+ * Which steps log: the log is enabled, total_it after the step is a multiple of `every`, and the call is
+ * td3_train_step, td3_train_step_batch, td3_train_step_batch_particles, td3_train_step_prioritized or
+ * td3_train_step_prioritized_particles (td3_probe_kernel's steps are td3_train_step calls and log).
+ * td3_actor_learn_particles (no critic step) and the step of td3_profile_stages never log.  Logged step
+ * number k = 0, 1, ... (the sequence number) goes to slot k mod capacity; `count` is the number logged so far.
+ * The launch is queued on the step's stream directly behind the step's body -- in a prioritized step behind
+ * the combine and the priority write-back -- and before the synchronisation a non-null `stats` forces.  It
+ * is always a direct launch, never part of a captured graph: the sequence number, `step` and the flags are
+ * kernel arguments the host knows, so the log needs no device counter and no atomics.
+ *
+ * The kernel reads only rows r < B of the step's buffers, never a pad row: y and Q1 ([B][nq], nq = 1 for a
+ * featured learner, action_dim for a particle learner); Q2 where the learner has a twin (featured learners
+ * always, particle learners with CDQ); the rows' squared errors of each critic as the loss rows wrote
+ * them (on prioritized steps weighted); Q1(s, pi(s)) on actor steps; the importance weights on prioritized
+ * steps.  All arithmetic is fp64 on the fp32 values widened, in one fixed order, so entries repeat bit
+ * for bit: the elements e = r * nq + o are numbered 0 .. B*nq - 1; thread p accumulates e = p, p + 256, ...
+ * in increasing order starting from 0.0; the 256 partials are combined through LDS by a halving tree
+ * (partial[p] += partial[p + s], s = 128, 64, ..., 1, rs_tick_kernel's tree); quantities per row use the
+ * same scheme over the rows r; min and max use the same partition and tree with < and >, threads without
+ * an element carrying +inf / -inf; a mean is the tree's sum divided once by the count.  Nothing is
+ * contracted into an fma: the only products are by 0.5 and 1 / (J*A), applied to a row's value before it
+ * enters a sum.  With n = B * nq, J critics (2 with a twin, else 1) and A = nq:
+ *   critic_loss   S_1 / n + S_2 / n, S_j the sum over rows of critic j's squared-error row (the second
+ *                 term only with a twin): td3_step_stats.critic_loss's formula, the weighted loss on
+ *                 prioritized steps
+ *   actor_loss    -(sum of Q1(s, pi(s))) / n on actor steps, NaN otherwise
+ *   q1_mean, q2_mean, y_mean; q_min, q_max over both critics; y_min, y_max
+ *   q_gap_mean    the mean of |Q1 - Q2| over the elements
+ *   td_abs_mean, td_abs_max   over the rows of t_r = 1/(J*A) sum_j sum_o |Q_j,r,o - y_r,o|, o in
+ *                 increasing order, the critics then added in order j (featured: 0.5 (|Q1 - y| + |Q2 - y|))
+ *   w_mean, w_min over the rows' importance weights on prioritized steps; exactly 1.0 otherwise, written
+ *                 without reading the buffer
+ *   nonfinite     the number of non-finite elements among y, Q1 and (with a twin) Q2
+ * Without a twin the q2 values repeat Q1's and q_gap_mean is 0.  Where nonfinite > 0 the other fields are
+ * whatever IEEE arithmetic gives; only nonfinite itself is specified.
+ *
+ * td3_log_enable: allocates the ring.  Data-parallel logging is out of scope: a handle in a td3_comm_init /
+ *   td3_comm_init_local group is refused, and both of those return -1 on a handle whose log is enabled.
+ * td3_log_info: a handle without the log reports enabled = 0 (and returns 0: this is the query for it).
+ * td3_log_read: rs_read_episodes' semantics -- the entries with sequence numbers in [first, first + n) that
+ *   are still in the ring (the last `capacity`), oldest first, into out; *first_out is the sequence number
+ *   of out[0], *n_out the entries written.  Synchronous: it waits for an event recorded behind the last
+ *   log launch (not for a stream: a caller's stream may be gone by then).
+ * td3_log_set: restores the last n <= capacity entries (sequence numbers count - n .. count - 1) and the
+ *   total `count`, for checkpoints; synchronous.  A run continued after it reads back exactly what the
+ *   uninterrupted run does.
+ * Checked in this order, each failure returning -1 before any GPU work with a message naming the field:
+ *   td3_log_enable: capacity in 1..2^20; every in 1..2^20; the handle; not already enabled; not in a
+ *     td3_comm_init or td3_comm_init_local group.
+ *   td3_log_read: first >= 0; n >= 0; out non-null unless n == 0; first_out; n_out; the handle; enabled.
+ *   td3_log_set: n >= 0; entries non-null unless n == 0; count >= n; the handle; enabled; n <= capacity.
+ *   td3_log_info: info non-null; the handle. */
+typedef struct td3_log_entry {
+  int64_t step;            /* total_it after the step */
+  int32_t batch;           /* B of the step */
+  int32_t actor_step;      /* 1 when the delayed policy update ran */
+  int32_t prioritized;     /* 1 for td3_train_step_prioritized(_particles) */
+  int32_t nonfinite;
+  double critic_loss, actor_loss;
+  double q1_mean, q2_mean, y_mean;
+  double q_min, q_max, y_min, y_max;
+  double q_gap_mean;
+  double td_abs_mean, td_abs_max;
+  double w_mean, w_min;
+} td3_log_entry;
+typedef struct td3_log_info_t {
+  int enabled, capacity, every;
+  int64_t count;           /* steps logged so far (the next sequence number) */
+} td3_log_info_t;
+/* sizeof(td3_log_entry) of this library: a binding checks its own struct against it. */
+size_t td3_log_entry_size(void);
+int td3_log_enable(td3_handle* h, int capacity, int every);
+int td3_log_info(const td3_handle* h, td3_log_info_t* info);
+int td3_log_read(td3_handle* h, int64_t first, int64_t n, td3_log_entry* out, int64_t* first_out,
+                 int64_t* n_out);
+int td3_log_set(td3_handle* h, const td3_log_entry* entries, int64_t n, int64_t count);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL) */
 int td3_comm_unique_id(unsigned char out[128]);
 /* Data-parallel mode: grads are all-reduced (sum, then /world) over RCCL before Adam.  Every
@@ -638,6 +727,11 @@ int td3_debug_plan_flags(const td3_handle* h, int* flags);
  * first prioritized step of the current plan on this ring.  The draw and the priority update are
  * rb_sample_prioritized and rb_update_priorities themselves. */
 int td3_debug_per_stage(td3_handle* h, rb_handle* rb, int stage, void* stream);
+/* Measurement instrumentation (tools/bench_train_log.py): queue on `stream` the training log's launch of
+ * the last logged step once more, over the plan's buffers as that step left them and into the same slot
+ * (the entry is rewritten with the same values; count does not move).  -1 unless the last step of this
+ * handle was logged. */
+int td3_debug_log_launch(td3_handle* h, void* stream);
 
 /* Test seam of the one-launch query's failure path: in the next n select_action / eval_q launches
  * (existing query plans) workgroup 0 acts as if its in-launch layer-1 poll had timed out.  The query

@@ -494,6 +494,20 @@ class TD3(TD3_base):
             out["weight"], out["td_abs"] = weight, td_abs
         return out
 
+    # ------------------------------------------------------------------ training log
+    def enable_train_log(self, capacity=4096, every=1):
+        """Keep per-step losses and Q statistics in a ring of ``capacity`` entries on the device, one
+        entry per step whose ``total_it`` is a multiple of ``every`` (``train_log.TrainLog``: one small
+        launch behind each logged step, nothing read back until asked).  Returns ``train_log``."""
+        from .train_log import TrainLog
+        self._train_log = TrainLog(self, capacity, every)
+        return self._train_log
+
+    @property
+    def train_log(self):
+        """The ``TrainLog`` of ``enable_train_log``; None before that call."""
+        return getattr(self, "_train_log", None)
+
     def sync(self):
         check(self._lib.td3_sync(self._h), "td3_sync")
 

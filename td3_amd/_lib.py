@@ -93,6 +93,19 @@ class rs_state(C.Structure):
                 ("ep_return_sum", C.c_double)]
 
 
+class td3_log_entry(C.Structure):
+    _fields_ = [("step", C.c_int64), ("batch", C.c_int32), ("actor_step", C.c_int32), ("prioritized", C.c_int32),
+                ("nonfinite", C.c_int32), ("critic_loss", C.c_double), ("actor_loss", C.c_double),
+                ("q1_mean", C.c_double), ("q2_mean", C.c_double), ("y_mean", C.c_double),
+                ("q_min", C.c_double), ("q_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double),
+                ("q_gap_mean", C.c_double), ("td_abs_mean", C.c_double), ("td_abs_max", C.c_double),
+                ("w_mean", C.c_double), ("w_min", C.c_double)]
+
+
+class td3_log_info_t(C.Structure):
+    _fields_ = [("enabled", C.c_int), ("capacity", C.c_int), ("every", C.c_int), ("count", C.c_int64)]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -167,6 +180,11 @@ SIGNATURES = {
     "td3_actor_learn_particles": (C.c_int, [_P, _P, _P, C.c_int, _P, _D]),
     "td3_select_action_particles": (C.c_int, [_P, _F, _F, _F, C.c_int]),
     "td3_eval_q_particles": (C.c_int, [_P, _F, _F, _F, _F, C.c_int]),
+    "td3_log_entry_size": (C.c_size_t, []),
+    "td3_log_enable": (C.c_int, [_P, C.c_int, C.c_int]),
+    "td3_log_info": (C.c_int, [_P, C.POINTER(td3_log_info_t)]),
+    "td3_log_read": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(td3_log_entry), _I64, _I64]),
+    "td3_log_set": (C.c_int, [_P, C.POINTER(td3_log_entry), C.c_int64, C.c_int64]),
     "td3_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "td3_comm_init": (C.c_int, [_P, C.POINTER(C.c_ubyte), C.c_int, C.c_int]),
     "td3_comm_init_local": (C.c_int, [C.POINTER(_P), C.c_int]),
@@ -185,6 +203,7 @@ SIGNATURES = {
     "td3_debug_activation": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "td3_debug_plan_flags": (C.c_int, [_P, _P]),
     "td3_debug_per_stage": (C.c_int, [_P, _P, C.c_int, _P]),
+    "td3_debug_log_launch": (C.c_int, [_P, _P]),
     "td3_debug_act_fail": (C.c_int, [_P, C.c_int]),
     "td3_last_error": (C.c_char_p, []),
 }

@@ -1,5 +1,5 @@
 // Internal header of the learner's translation units (td3.hip, stages.hip, step.hip, act.hip, dp.hip,
-// debug.hip): the types they share and the functions that cross a file boundary.  Functions used in
+// debug.hip, trainlog.hip): the types they share and the functions that cross a file boundary.  Functions used in
 // one file are static there.
 #pragma once
 #include <rccl/rccl.h>
@@ -281,6 +281,22 @@ struct PolicyDst {
   int clamp; float max_action;
 };
 
+// The training log of a handle (include/td3.h, "training log"; trainlog.hip): a ring of `cap` entries in
+// device memory.  `count` steps were logged so far; ev is recorded behind every log launch on the
+// step's stream, so a read waits for the last one without holding a caller's stream.
+struct TrainLog {
+  int cap = 0, every = 1;
+  int64_t count = 0;
+  int64_t floor = 0;       // the oldest sequence number td3_log_set restored (0: none lost that way)
+  td3_log_entry* d = nullptr;
+  hipEvent_t ev = nullptr;
+  bool ev_recorded = false;
+  // the last logged step, for td3_debug_log_launch: its flags, its total_it and the plan whose buffers it read
+  bool last_actor = false, last_prioritized = false;
+  int64_t last_step = 0;
+  const Plan* last_plan = nullptr;
+};
+
 struct EncItem {
   const NetL* net;
   const float* P;         // group arena (encoder at P + net->enc_off)
@@ -349,6 +365,7 @@ struct td3_handle {
   int probe_used = 0;
   std::vector<std::string> stage_names;
   std::vector<std::string> stage_kernels;
+  std::unique_ptr<td3::TrainLog> log;         // td3_log_enable; null: steps queue nothing for it
 };
 
 namespace td3 {
@@ -416,9 +433,12 @@ int ensure_unit_weights(td3_handle* h, hipStream_t s);
 int build_plan(td3_handle* h, int B);
 int ensure_plan(td3_handle* h, int B);
 int bind_ring(td3_handle* h, Ring* r);
-int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* stats);
+int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* stats, bool prioritized = false);
 enum RingUser : int { kLearnerStep = 0, kReplicaStep = 1 };
 int check_ring(const td3_handle* h, const Ring* r, RingUser what);
+// ---- trainlog.hip
+int log_step(td3_handle* h, int actor_phase, bool prioritized, hipStream_t s);
+void destroy_train_log(td3_handle* h);
 // ---- act.hip
 int map_io(ActPlan* A, size_t floats, IoCarve* io);
 // ---- dp.hip

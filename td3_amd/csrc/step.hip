@@ -900,7 +900,7 @@ static int note_actor_update(td3_handle* h, hipStream_t s) {
   return 0;
 }
 
-int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* stats) {
+int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* stats, bool prioritized) {
   h->total_it += 1;
   h->critic_step += 1;
   h->last_step_stream = s;
@@ -908,6 +908,8 @@ int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* s
     h->actor_step += 1;
     TD3_RC(note_actor_update(h, s));
   }
+  // the training log's launch: behind the body (and a prioritized step's write-back), ahead of the sync
+  if (h->log && h->total_it % h->log->every == 0) TD3_RC(log_step(h, actor_phase, prioritized, s));
   if (!stats) return 0;
   Plan* P = h->plan.get();
   TD3_HIP(hipStreamSynchronize(s));
@@ -1026,7 +1028,7 @@ static int prioritized_step(td3_handle* h, rb_handle* rbh, int batch, double bet
   TD3_RC(ring_store_priorities(r, P->d_inject_idx, P->per_td, batch, true, s));
   TD3_RC(ring_end_read(r, s));                   // later adds wait for the step and its write-back
   if (inject_u || inject_noise) TD3_HIP(hipStreamSynchronize(s));   // host sources are pageable
-  TD3_RC(finish_step(h, actor_phase, s, stats));
+  TD3_RC(finish_step(h, actor_phase, s, stats, true));
   if (per && (per->weight || per->td_abs)) {
     TD3_HIP(hipStreamSynchronize(s));
     if (per->weight) TD3_HIP(hipMemcpy(per->weight, P->per_w, (size_t)batch * 4, hipMemcpyDeviceToHost));

@@ -267,6 +267,7 @@ int td3_destroy(td3_handle* h) {
   (void)hipStreamSynchronize(h->act_stream);
   ring_forget_stream(h->stream);        // rings that noted it as their reader / writer
   if (h->plan) destroy_plan(h->plan.get());
+  destroy_train_log(h);
   // a device-resident query on a caller's stream may still read its plan and the parameters
   if (h->dev_stream && h->dev_stream != h->stream) (void)hipStreamSynchronize(h->dev_stream);
   if (h->dev_ev) (void)hipEventDestroy(h->dev_ev);
