@@ -42,6 +42,10 @@
  *   td3_log_enable / td3_log_info / td3_log_read / td3_log_set
  *                        the training log (no counterpart in the reference): per-step losses and Q
  *                        statistics of either learner in a device ring, one opt-in launch per logged step
+ *   td3_set_bc / td3_bc_info
+ *                        TD3+BC (Fujimoto & Gu 2021; no counterpart in the reference): the behaviour-cloning
+ *                        term of the featured actor step, for buffers the learner did not collect
+ *                        (experience_injection.py, main.py --load_replay_buffer)
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -653,6 +657,59 @@ int td3_log_read(td3_handle* h, int64_t first, int64_t n, td3_log_entry* out, in
                  int64_t* n_out);
 int td3_log_set(td3_handle* h, const td3_log_entry* entries, int64_t n, int64_t count);
 
+/* ------------------------------------------------------------------ TD3+BC (offline data) */
+/* The behaviour-cloning term of TD3+BC (Fujimoto & Gu 2021, "A Minimalist Approach to Offline
+ * Reinforcement Learning") in the actor step of a featured learner, every norm, one device.  The
+ * reference's workflow it serves: a buffer filled from a recorded policy (experience_injection.py) and
+ * main.py --load_replay_buffer, which trains on the loaded rows from the first tick.  On a step whose
+ * delayed policy update runs, with alpha > 0, B rows, A = action_dim, pi_r = max_action tanh(z4_r) as the
+ * step's actor forward computed it, a_r the batch's stored action and Q_r = Q1(s_r, pi_r) with the critic
+ * as the step's critic update left it:
+ *   q_abs_mean = 1/B sum_r |Q_r|                        (no gradient flows through it)
+ *   lambda     = alpha / q_abs_mean
+ *   loss       = -lambda 1/B sum_r Q_r + 1/(B*A) sum_r sum_o (pi_r,o - a_r,o)^2
+ *   dL/dpi_r,o = lambda g_r,o + 2/(B*A) (pi_r,o - a_r,o)
+ * g_r,o is dQ1/da_o of the plain step (through Q1's layer 0, carrying -1/B).  Everything behind dL/dpi is
+ * the plain step's: tanh backward, the actor head, LN3 backward, the input-grad stages, dW, Adam, Polyak.
+ * The critic phase is untouched; in td3_train_step_prioritized the importance weights still touch only
+ * the critic.  All of it is float32 on the device: sum_r |Q_r| runs over the rows r < B only, never a pad
+ * row, in one fixed order (lane l of one wave adds rows l, l + 64, ... ascending from 0.0f, the 64
+ * partials through the wave's fixed reduction tree), divided once by (float)B; lambda = (float)alpha /
+ * that.  Every wave that needs lambda uses those bits, whatever the grid, the head path (narrow / wide)
+ * or the launch mode (graph / direct).  q_abs_mean == 0 gives lambda = inf as the paper's code does:
+ * there is NO guard.  Each row's sum_o (pi - a)^2 is added in increasing o.
+ * The stored action is read from the step's [s | a] batch rows, which every input path fills (ring sample
+ * fused into the first layer or gathered, injected indices, td3_train_step_batch).
+ *
+ * td3_set_bc: alpha = 0 turns the term off.  Synchronises the learner and, when alpha changes, rebuilds
+ *   the step plan and its captured graphs (alpha, B and A are launch arguments; lambda itself is computed
+ *   on the device, so the graphs replay unchanged).  With alpha == 0, or on a handle never touched, the
+ *   step is exactly the plain one: the same stage list, the same kernels, the same bits.  With alpha > 0
+ *   the actor phase runs the BC form of the actor_head_bwd stage (td3_stage_kernel names it); nothing
+ *   else in the stage list changes.  Every single-device featured step entry point takes it:
+ *   td3_train_step, td3_train_step_batch, td3_train_step_prioritized, td3_probe_kernel,
+ *   td3_profile_stages.
+ *   Returns -1 with a message, before any GPU work, for (checked in this order): alpha negative or
+ *   non-finite; a null handle; a particle handle (the particle learner has no BC step yet); a handle in a td3_comm_init or
+ *   td3_comm_init_local group -- and both of those refuse a handle with BC on: lambda would need the
+ *   global batch's mean.
+ * td3_step_stats.actor_loss and the training log's actor_loss keep their meaning with BC on:
+ *   -mean Q1(s, pi(s)), not the BC loss.  No struct layout changes.
+ * td3_bc_info: synchronous; with a BC step to report it waits for the whole device (hipDeviceSynchronize: that
+ *   step may sit on a caller's stream the handle no longer knows to be alive).  `step` is total_it of the last actor
+ *   step taken with BC in the current step plan, 0 if none (a plan rebuild -- td3_set_bc, another batch
+ *   size, td3_set_adam -- forgets it); lambda and q_abs_mean are that step's float32 values widened;
+ *   bc_loss = (sum over r < B, in row order, of the row sums widened to fp64) / (B*A).  With step == 0
+ *   the three are 0.  Returns -1 for a null info, then a null handle. */
+typedef struct td3_bc_info_t {
+  int enabled;
+  double alpha;
+  int64_t step;
+  double lambda, q_abs_mean, bc_loss;
+} td3_bc_info_t;
+int td3_set_bc(td3_handle* h, double alpha);
+int td3_bc_info(td3_handle* h, td3_bc_info_t* info);
+
 /* ------------------------------------------------------------------ multi-GPU (RCCL) */
 int td3_comm_unique_id(unsigned char out[128]);
 /* Data-parallel mode: grads are all-reduced (sum, then /world) over RCCL before Adam.  Every
@@ -738,6 +795,11 @@ int td3_debug_log_launch(td3_handle* h, void* stream);
  * must then fail (rc < 0, the kernel publishes its flag with the failure bit) and the next query must
  * be correct again (the host re-zeroes the hand-off counters). */
 int td3_debug_act_fail(td3_handle* h, int n);
+/* Test seam of the wide heads (action width > 8): the dynamic LDS bytes of the calling thread's last row-kernel
+ * launch, i.e. of the weight rows its workgroups staged (0: every head was requested block by block, e.g.
+ * under TD3_WIDE_HEADS=0; -1: no row launch yet).  Launches replayed from a captured graph do not count: use it
+ * behind a direct launch (td3_profile_stages, use_graph = 0). */
+int td3_debug_row_lds(void);
 
 const char* td3_last_error(void);
 

@@ -197,7 +197,7 @@ class TD3(TD3_base):
 
     def __init__(self, obs_space, action_space, max_action=1, lr=1e-4, norm=None, CDQ=True,
                  device=None, seed=0, use_graph="auto", actor_arch=ACTOR_ARCH, q_arch=Q_ARCH,
-                 init="torch", **kwargs):
+                 init="torch", bc_alpha=None, **kwargs):
         super().__init__(max_action=max_action, **kwargs)
         self._lib = _lib.load()
         if norm not in (None, "layer", "weight_normalization"):
@@ -241,6 +241,10 @@ class TD3(TD3_base):
         if init == "torch":
             a0, c0 = torch_default_init(sd, ad, norm, actor_arch, q_arch)
             self.set_weights(a0, c0)
+        # TD3+BC (Fujimoto & Gu 2021) for offline / demonstration-heavy buffers: the weight of the Q term
+        # is bc_alpha / mean |Q|, next to an MSE between the policy's and the stored action (None / 0: off)
+        if bc_alpha:
+            self.bc_alpha = bc_alpha
 
     # ------------------------------------------------------------------ plumbing
     def _query_tensors(self, g):
@@ -294,6 +298,26 @@ class TD3(TD3_base):
     def total_it(self, v):
         t, c, a = self._counters()
         self._set_counters(v, c, a)
+
+    @property
+    def bc_alpha(self):
+        """TD3+BC's ``alpha`` (2.5 in the paper), None when the behaviour-cloning term is off.  Setting it
+        (None or 0: off) synchronises the learner and rebuilds its step plan (``td3_set_bc``)."""
+        return getattr(self, "_bc_alpha", None)
+
+    @bc_alpha.setter
+    def bc_alpha(self, v):
+        a = 0.0 if v is None else float(v)
+        check(self._lib.td3_set_bc(self._h, a), "td3_set_bc")
+        self._bc_alpha = a if a > 0 else None
+
+    def bc_info(self):
+        """``td3_bc_info`` as a dict: ``enabled``, ``alpha``, ``step`` (``total_it`` of the last actor step
+        taken with BC, 0 if none), ``lambda``, ``q_abs_mean``, ``bc_loss``.  Synchronous."""
+        info = _lib.td3_bc_info_t()
+        check(self._lib.td3_bc_info(self._h, C.byref(info)), "td3_bc_info")
+        return {"enabled": bool(info.enabled), "alpha": info.alpha, "step": info.step, "lambda": getattr(info, "lambda"),
+                "q_abs_mean": info.q_abs_mean, "bc_loss": info.bc_loss}
 
     def set_weights(self, actor, critic, actor_target=None, critic_target=None):
         """Load numpy/torch state dicts; targets default to copies (TD3_featured.py:102,107)."""
@@ -423,7 +447,9 @@ class TD3(TD3_base):
         prioritized ring (``enable_priorities``) without ``indices`` the step draws its rows by
         priority, weights the critic loss with ``per_beta`` and writes the new priorities back, all on
         the device; ``u`` (``[batch_size]`` mass fractions) replaces that draw and the stats gain
-        ``"weight"`` and ``"td_abs"``."""
+        ``"weight"`` and ``"td_abs"``.  With ``bc_alpha`` set, the stats of an actor step gain
+        ``"bc_lambda"``, ``"bc_q_abs_mean"``, ``"bc_loss"`` and ``"bc_actor_loss"`` (= -lambda mean Q +
+        bc_loss; ``"actor_loss"`` keeps its meaning, -mean Q)."""
         B = int(batch_size)
         st = None
         keep = []
@@ -490,6 +516,11 @@ class TD3(TD3_base):
                "y": keep[0], "q1": keep[1], "q2": keep[2], "idx": keep[3], "noise": keep[4]}
         if st.actor_step:
             out["actor_loss"] = st.actor_loss
+            if self.bc_alpha:
+                # actor_loss stays -mean Q1(s, pi(s)); the loss the actor descended is bc_actor_loss
+                bi = self.bc_info()
+                out["bc_lambda"], out["bc_q_abs_mean"], out["bc_loss"] = bi["lambda"], bi["q_abs_mean"], bi["bc_loss"]
+                out["bc_actor_loss"] = bi["lambda"] * st.actor_loss + bi["bc_loss"]
         if prioritized:
             out["weight"], out["td_abs"] = weight, td_abs
         return out

@@ -102,6 +102,11 @@ class td3_log_entry(C.Structure):
                 ("w_mean", C.c_double), ("w_min", C.c_double)]
 
 
+class td3_bc_info_t(C.Structure):
+    _fields_ = [("enabled", C.c_int), ("alpha", C.c_double), ("step", C.c_int64), ("lambda", C.c_double),
+                ("q_abs_mean", C.c_double), ("bc_loss", C.c_double)]
+
+
 class td3_log_info_t(C.Structure):
     _fields_ = [("enabled", C.c_int), ("capacity", C.c_int), ("every", C.c_int), ("count", C.c_int64)]
 
@@ -185,6 +190,8 @@ SIGNATURES = {
     "td3_log_info": (C.c_int, [_P, C.POINTER(td3_log_info_t)]),
     "td3_log_read": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(td3_log_entry), _I64, _I64]),
     "td3_log_set": (C.c_int, [_P, C.POINTER(td3_log_entry), C.c_int64, C.c_int64]),
+    "td3_set_bc": (C.c_int, [_P, C.c_double]),
+    "td3_bc_info": (C.c_int, [_P, C.POINTER(td3_bc_info_t)]),
     "td3_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "td3_comm_init": (C.c_int, [_P, C.POINTER(C.c_ubyte), C.c_int, C.c_int]),
     "td3_comm_init_local": (C.c_int, [C.POINTER(_P), C.c_int]),
@@ -204,6 +211,7 @@ SIGNATURES = {
     "td3_debug_plan_flags": (C.c_int, [_P, _P]),
     "td3_debug_per_stage": (C.c_int, [_P, _P, C.c_int, _P]),
     "td3_debug_log_launch": (C.c_int, [_P, _P]),
+    "td3_debug_row_lds": (C.c_int, []),
     "td3_debug_act_fail": (C.c_int, [_P, C.c_int]),
     "td3_last_error": (C.c_char_p, []),
 }

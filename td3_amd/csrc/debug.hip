@@ -52,6 +52,7 @@ int td3_profile_stages(td3_handle* h, rb_handle* rbh, int batch, int actor_phase
   h->total_it += 1;
   h->critic_step += 1;
   if (actor_phase) h->actor_step += 1;   // (stream synchronised above: no actor event needed)
+  note_bc_step(h, actor_phase);
   return 0;
 }
 
@@ -111,6 +112,8 @@ int td3_debug_plan_flags(const td3_handle* h, int* flags) {
   *flags = h->plan ? ((h->plan->w4 ? 1 : 0) | (h->dp_sharded ? 2 : 0)) : 0;
   return 0;
 }
+
+int td3_debug_row_lds(void) { return last_row_lds(); }
 
 int td3_debug_act_fail(td3_handle* h, int n) {
   TD3_ARG(h && n >= 0, "bad argument");

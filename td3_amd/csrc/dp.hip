@@ -124,6 +124,7 @@ int td3_comm_init(td3_handle* h, const unsigned char id[128], int nranks, int ra
   TD3_ARG(h && id, "null argument");
   TD3_ARG(nranks >= 1 && rank >= 0 && rank < nranks, "bad rank / nranks");
   TD3_ARG(!h->log, "the training log is enabled on this handle (data-parallel logging is not supported)");
+  TD3_ARG(h->bc_alpha == 0.0, "TD3+BC is on for this handle (td3_set_bc): data-parallel BC is not supported");
   TD3_HIP(hipSetDevice(h->cfg.device));
   ncclUniqueId uid;
   memcpy(&uid, id, 128);
@@ -157,6 +158,7 @@ int td3_comm_init_local(td3_handle** hs, int n) {
     TD3_ARG(hs[k] != nullptr, "null handle");
     TD3_ARG(!hs[k]->comm && !hs[k]->local, "handle already in a data-parallel group");
     TD3_ARG(!hs[k]->log, "the training log is enabled on a handle (data-parallel logging is not supported)");
+    TD3_ARG(hs[k]->bc_alpha == 0.0, "TD3+BC is on for a handle (td3_set_bc): data-parallel BC is not supported");
     TD3_ARG(hs[k]->cfg.device == hs[0]->cfg.device, "local replicas share one device");
     TD3_ARG(hs[k]->particles == hs[0]->particles && hs[k]->actor.size == hs[0]->actor.size &&
                 hs[k]->critic.size == hs[0]->critic.size && hs[k]->cfg.norm == hs[0]->cfg.norm,

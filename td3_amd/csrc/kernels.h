@@ -52,6 +52,7 @@ enum RowKind : int {
   kRowUnitLoss = 7,      // Q_j head, LN3 of Q_j, unit dU3 / dZ3 rows of Q_j
   kRowTargetLoss = 8,    // target heads -> y (:140-142), g_j = 2/B (Q_j - y) (:148), squared errors
   kRowLnBwd = 9,         // dZ = relu'(LN_bwd(dU)) of full rows (layer 0, no GEMM follows)
+  kRowActorHeadBwdBc = 10,   // kRowActorHeadBwd of the TD3+BC actor loss: dL/dpi = lambda dQ1/da + 2/(B A) (pi - a)
 };
 
 // ------------------------------------------------------------------ operand slots
@@ -212,6 +213,29 @@ enum : int {
 };
 }  // namespace actor_head_bwd
 TD3_SLOTS_FIT(actor_head_bwd);
+
+// kRowActorHeadBwdBc (row_actor_head_bwd<.., BC = true>): kRowActorHeadBwd's operands, then those of the
+// behaviour-cloning term (td3_set_bc, include/td3.h)
+namespace actor_head_bwd_bc {
+using namespace actor_head_bwd;
+enum : int {
+  kQv = actor_head_bwd::kNumPtr,   // Q1(s, pi(s)) of the rows [Bp] (pro_headbwd wrote them): lambda = alpha / mean |Q|
+  kAct,          // the batch's [s | a] rows (ld kLdAct): the stored action at columns kActCol..
+  kRowSe,        // out: sum over o of (pi_o - a_o)^2 of a live row, 0 for a pad row [Bp]
+  kLam,          // out (row 0, lane 0): (lambda, mean |Q|), 2 floats
+  kNumPtr
+};
+enum : int {
+  kLdAct = actor_head_bwd::kNumInt,
+  kNumInt
+};
+enum : int {
+  kAlpha = actor_bwd::kNumFlt,
+  kBcScale,      // 2/(B A)
+  kNumFlt
+};
+}  // namespace actor_head_bwd_bc
+TD3_SLOTS_FIT(actor_head_bwd_bc);
 
 // kRowActorHeadBwdP (row_actor_head_bwd_p): dQ1/da through lnorm1 of the Q1 input
 namespace actor_head_bwd_p {
@@ -597,6 +621,11 @@ int launch_rows(int kind, const GemmTable& t, int Bp, hipStream_t s);
 // Two row kinds in one launch: problems [0, n1) run kind1, [n1, nprob) kind2.
 int launch_rows2(int kind1, int kind2, int n1, const GemmTable& t, int Bp, hipStream_t s);
 int launch_heads(const HeadArgs& a, int nprob, hipStream_t s);
+// kRowActorHeadBwdBc (bc.hip), called by launch_rows with the table's wide problems marked and the stage's bytes
+int launch_rows_bc(const GemmTable& d, int lds, int Bp, hipStream_t s);
+// Dynamic LDS bytes of the calling thread's last launch_rows / launch_rows2 (the wide-head stage;
+// 0: every head was requested block by block; -1: no row launch yet): td3_debug_row_lds
+int last_row_lds();
 int launch_lnbwd_rows(const LnBwdTable& tab, int nprob, int Bp, int norm, hipStream_t s);
 int launch_dw(const DwArgs& a, int nblocks, hipStream_t s);
 // The flat optimizer's view of the images: the range it updates starts at arena offset `base`; a

@@ -27,6 +27,7 @@
 
 #include "dev.h"
 #include "kernels.h"
+#include "row_actor.h"
 
 namespace td3 {
 
@@ -83,16 +84,6 @@ __device__ unsigned long long td3_clk_sum[2];
 // memory clobber keeps the compiler from moving LDS accesses across it; global memory needs no
 // ordering at these barriers (no workgroup reads global data another of its waves stored).
 // TD3_SYNC_BARRIERS=1 restores __syncthreads() (A/B builds).
-#ifndef TD3_SYNC_BARRIERS
-#define TD3_SYNC_BARRIERS 0
-#endif
-__device__ __forceinline__ void lds_barrier() {
-#if TD3_SYNC_BARRIERS
-  __syncthreads();
-#else
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
 
 __device__ __forceinline__ void lds_put_row(float* smem, int S, int row, int Kp, int lane, const float (&v)[8]) {
   lds_store8(smem + row * S, Kp, lane, v);
@@ -510,48 +501,6 @@ __device__ __forceinline__ void l0_store_rows(const GemmProb& P, const float* sm
 // One batch row per wave (grid: Bp/4 x nprob, 256 threads): the head / loss work between the
 // GEMM stages.  Every operand of the row (and the head weights) is requested up front, the
 // reductions are DPP wave sums; a wave's serial chain is a single row.
-struct RowCtx {
-  int row, lane, Bp;
-};
-
-// ---- policy heads: target smoothing (TD3_featured.py:131-137) / pi(s) = ma*tanh (:47-48) --
-// (operands: policy_head, kernels.h)
-constexpr int kHeadRegs = 8;   // head outputs kept in registers (wider heads loop)
-
-// Wide heads (action width > kHeadRegs; Humanoid: 17).  Requested block by block, the head weight
-// rows cost one dependent load round trip per kHeadRegs outputs (actor_head_bwd: a wave's chain
-// 8 us at Humanoid B = 1024, profiles/r05_timeline_humanoid.txt).  Instead the workgroup stages
-// every row once in (dynamic) LDS, all requests in one round trip, shared by its kWideRows rows
-// (RW: the launch's rows per workgroup); launch_rows sizes the LDS, launches the RW = kWideRows
-// variant and marks the problems (GemmProb::tile_begin = 1, otherwise unused by the row kernels).
-// The LDS rows are the same values, used in the same order: bit-identical results.
-constexpr int kWideStage = 16;   // float4 per thread: up to 64 KB staged by kWideRows waves
-constexpr int kWideRows = 4;     // rows (waves) per workgroup of the wide-head row launches
-// The row operands, re-defined after the stage: the wide and narrow paths' identical LayerNorm math
-// on them was hoisted above the branch, i.e. waited for the rows before the stage was requested
-__device__ __forceinline__ void opaque8(float (&v)[8]) {
-  asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-}
-__device__ __forceinline__ void opaque1(float& v) { asm volatile("" : "+v"(v)); }
-template <int NT>
-__device__ __forceinline__ void wide_stage(float4* dst, const float4* a, int n1, const float4* b, int n2) {
-  const int n = n1 + n2;
-  // surplus slots re-copy element `spare` (distinct per lane): unconditional loads and stores, so
-  // the compiler cannot sink the loads into per-slot branches (one round trip per slot)
-  const int spare = (int)threadIdx.x < n ? (int)threadIdx.x : 0;
-  float4 v[kWideStage];
-  int at[kWideStage];
-#pragma unroll
-  for (int i = 0; i < kWideStage; ++i) {
-    const int e = (int)threadIdx.x + NT * i;
-    at[i] = e < n ? e : spare;
-    v[i] = at[i] < n1 ? a[at[i]] : b[at[i] - n1];
-  }
-#pragma unroll
-  for (int i = 0; i < kWideStage; ++i) dst[at[i]] = v[i];
-  lds_barrier();
-}
-
 template <bool NORM, int RW = 1>
 __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx& c) {
   using namespace policy_head;
@@ -680,166 +629,6 @@ __device__ __forceinline__ void row_policy_head(const GemmProb& P, const RowCtx&
   }
   gst(P.ex[kOut] + ((size_t)c.row * P.exi[kLdOut] + sd + o), live ? a : 0.f);
   if (P.ex[kOut2]) gst(P.ex[kOut2] + ((size_t)c.row * P.exi[kLdOut] + sd + o), live ? a : 0.f);
-}
-
-// W[:, s0 .. s0+kHeadRegs): those columns of the 8 W rows a lane owns (rcol), as two float4 loads
-// per row at the (4-B aligned) column s0 itself; columns at or past `lim` are 0.  (Aligned loads
-// from below s0 needed a select on the uniform offset, which compiled to branches with a full
-// load drain per row: 8 dependent load round trips.)
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ void head_cols(const float* W, int ldw, int s0, int lim, int lane,
-                                          float (&out)[kHeadRegs][8]) {
-  static_assert(kHeadRegs == 8, "two float4 per row");
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) {
-    const float* wp = W + ((size_t)rcol(lane, jj) * ldw + s0);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const f32x4u t = *reinterpret_cast<const f32x4u*>(wp + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) out[4 * q + e][jj] = 4 * q + e < lim ? t[e] : 0.f;
-    }
-  }
-}
-
-// ---- dQ1/da through Q1's first layer, then the actor's head and LN3 backward -------------
-// (operands: actor_head_bwd, kernels.h)
-template <bool NORM, int RW = 1>
-__device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowCtx& c) {
-  using namespace actor_head_bwd;
-  // every field in one scalar-load batch (left alone, the compiler requested them where used, in
-  // dependent kernel-argument round trips between the row's loads)
-  asm volatile("" ::"s"(P.ex[kDU0]), "s"(P.ex[kH0]), "s"(P.ex[kStats0]), "s"(P.ex[kGamma0]), "s"(P.ex[kW1]),
-               "s"(P.ex[kTanh]), "s"(P.ex[kW4]), "s"(P.ex[kH3]), "s"(P.ex[kStats3]), "s"(P.ex[kGamma3]),
-               "s"(P.ex[kDZ4]), "s"(P.ex[kDU3]), "s"(P.ex[kW1T]), "s"(P.exi[kK0]), "s"(P.exi[kLd0]),
-               "s"(P.exi[kLdw1]), "s"(P.exi[kActCol]), "s"(P.exi[kAd]), "s"(P.exi[kK3]), "s"(P.exi[kLd3]),
-               "s"(P.exi[kLdw4]), "s"(P.exi[kLdW1T]), "s"(P.exf[kMaxAction]), "s"(P.Aout), "s"(P.ldao), "s"(P.B),
-               "s"(P.tile_begin));
-  const int K0 = P.exi[kK0], ld0 = P.exi[kLd0], ldw1 = P.exi[kLdw1], sd = P.exi[kActCol], ad = P.exi[kAd];
-  const int K3 = P.exi[kK3], ld3 = P.exi[kLd3], ldw4 = P.exi[kLdw4];
-  const float ma = P.exf[kMaxAction];
-  float gu0[1][8], h0[1][8], h3[1][8], g0[8], g3[8], mn0[1], rs0[1], mn3[1], rs3[1];
-  float w1[kHeadRegs][8], w4[kHeadRegs][8];
-  rv_load(gu0[0], P.ex[kDU0] + (size_t)c.row * ld0, ld0, c.lane);
-  rv_load(h0[0], P.ex[kH0] + (size_t)c.row * ld0, ld0, c.lane);
-  rv_load(h3[0], P.ex[kH3] + (size_t)c.row * ld3, ld3, c.lane);
-  if (NORM) {
-    rv_load(g0, P.ex[kGamma0], ld0, c.lane);
-    rv_load(g3, P.ex[kGamma3], ld3, c.lane);
-    mn0[0] = gld(P.ex[kStats0] + c.row);
-    rs0[0] = gld(P.ex[kStats0] + (c.Bp + c.row));
-    mn3[0] = gld(P.ex[kStats3] + c.row);
-    rs3[0] = gld(P.ex[kStats3] + (c.Bp + c.row));
-  } else {
-    mn0[0] = mn3[0] = 0.f;
-    rs0[0] = rs3[0] = 1.f;
-  }
-  const float tl = c.lane < ad ? gld(P.ex[kTanh] + ((size_t)c.row * 32 + c.lane)) : 0.f;
-  // W1[:, sd+o], the action columns: rows of the transposed copy when the step keeps one (kW1T,
-  // row length kLdW1T: coalesced, the same elements per lane), else strided column reads
-  const float* w1t = P.ex[kW1T];
-  if (RW > 1 && P.tile_begin) {     // wide head (wide_stage): the transposed W1 rows, then W4's, in LDS
-    extern __shared__ float4 row_lds4[];
-    const int n1 = ad * P.exi[kLdW1T] / 4;
-    wide_stage<64 * RW>(row_lds4, reinterpret_cast<const float4*>(w1t), n1, reinterpret_cast<const float4*>(P.ex[kW4]),
-               ad * ldw4 / 4);
-    const float* hw1 = reinterpret_cast<const float*>(row_lds4);
-    const float* hw4 = hw1 + (size_t)4 * n1;
-    opaque8(gu0[0]); opaque8(h0[0]); opaque8(h3[0]); opaque8(g0); opaque8(g3);
-    opaque1(mn0[0]); opaque1(rs0[0]); opaque1(mn3[0]); opaque1(rs3[0]);
-    ln_bwd_rows<1>(gu0, h0, g0, mn0, rs0, K0, c.lane, NORM);       // dZ0 of Q1 (pads -> 0)
-    const bool live = c.row < P.B;
-    float gu3[1][8];
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) gu3[0][jj] = 0.f;
-    for (int ob = 0; ob < ad; ob += kHeadRegs) {
-      float pb[kHeadRegs];
-#pragma unroll
-      for (int o = 0; o < kHeadRegs; ++o) {
-        float w[8];
-        rv_load_lds(w, hw1 + (size_t)(ob + o < ad ? ob + o : 0) * P.exi[kLdW1T], K0, c.lane);
-        pb[o] = rv_pdot(gu0[0], w, K0, c.lane);
-      }
-#pragma unroll
-      for (int o = 0; o < kHeadRegs; ++o)
-        if (ob + o < ad) {
-          const float ga = wsum(pb[o]);                               // dL/da_o
-          const float t = __shfl(tl, ob + o, 64);
-          const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;   // max_action*tanh bwd
-          if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + ob + o), gz4);
-          float w4r[8];
-          rv_load_lds(w4r, hw4 + (size_t)(ob + o) * ldw4, ldw4, c.lane);
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4r[jj];
-        }
-    }
-    rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
-    ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);        // dZ3 of the actor
-    rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
-    return;
-  }
-  if (w1t) {
-#pragma unroll
-    for (int o = 0; o < kHeadRegs; ++o) rv_load(w1[o], w1t + (size_t)(o < ad ? o : 0) * P.exi[kLdW1T], K0, c.lane);
-  } else {
-    head_cols(P.ex[kW1], ldw1, sd, ad, c.lane, w1);
-  }
-#pragma unroll
-  for (int o = 0; o < kHeadRegs; ++o) {
-    const int oo = o < ad ? o : 0;
-    rv_load(w4[o], P.ex[kW4] + (size_t)oo * ldw4, ldw4, c.lane);
-  }
-  ln_bwd_rows<1>(gu0, h0, g0, mn0, rs0, K0, c.lane, NORM);       // dZ0 of Q1 (pads -> 0)
-  const bool live = c.row < P.B;
-  float gu3[1][8];
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) gu3[0][jj] = 0.f;
-  float part[kHeadRegs];
-#pragma unroll
-  for (int o = 0; o < kHeadRegs; ++o) part[o] = rv_pdot(gu0[0], w1[o], K0, c.lane);
-#pragma unroll
-  for (int o = 0; o < kHeadRegs; ++o)
-    if (o < ad) {
-      const float ga = wsum(part[o]);                                 // dL/da_o
-      const float t = __shfl(tl, o, 64);
-      const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;       // max_action*tanh bwd
-      if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + o), gz4);
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4[o][jj];
-    }
-  // wide action spaces (Humanoid: 17): further blocks of kHeadRegs outputs, each block's W1
-  // columns and W4 rows requested in one batch (one load round trip per block, not per output)
-  for (int ob = kHeadRegs; ob < ad; ob += kHeadRegs) {
-    float w1b[kHeadRegs][8], w4b[kHeadRegs][8];
-    if (w1t) {
-#pragma unroll
-      for (int o = 0; o < kHeadRegs; ++o)
-        rv_load(w1b[o], w1t + (size_t)(ob + o < ad ? ob + o : 0) * P.exi[kLdW1T], K0, c.lane);
-    } else {
-      head_cols(P.ex[kW1], ldw1, sd + ob, ad - ob, c.lane, w1b);
-    }
-#pragma unroll
-    for (int o = 0; o < kHeadRegs; ++o) {
-      const int oo = ob + o < ad ? ob + o : 0;
-      rv_load(w4b[o], P.ex[kW4] + (size_t)oo * ldw4, ldw4, c.lane);
-    }
-    float pb[kHeadRegs];
-#pragma unroll
-    for (int o = 0; o < kHeadRegs; ++o) pb[o] = rv_pdot(gu0[0], w1b[o], K0, c.lane);
-#pragma unroll
-    for (int o = 0; o < kHeadRegs; ++o)
-      if (ob + o < ad) {
-        const float ga = wsum(pb[o]);
-        const float t = __shfl(tl, ob + o, 64);
-        const float gz4 = live ? (ga * ma) * (1.f - t * t) : 0.f;
-        if (c.lane == 0) gst(P.ex[kDZ4] + ((size_t)c.row * 32 + ob + o), gz4);
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) gu3[0][jj] += gz4 * w4b[o][jj];
-      }
-  }
-  rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
-  ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);        // dZ3 of the actor
-  rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
 }
 
 // ================================================================== TD3_particles heads
@@ -1004,10 +793,6 @@ __device__ __forceinline__ void row_actor_head_bwd_p(const GemmProb& P, const Ro
   rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
 }
 
-#ifndef TD3_ROW_WAVES
-#define TD3_ROW_WAVES 1
-#endif
-constexpr int kRowWaves = TD3_ROW_WAVES;   // waves (rows) per row-kernel workgroup: 1 (A/B 4 / 2 / 1: C2 8.93k / 9.03k / 9.09k; the waves of a row stage spread over 4x the CUs, whose load units they no longer share)
 // ---- unit-gradient critic head (kRowUnitLoss) ----------------------------------------------
 // The Q_j head (TD3_featured.py:145, Q.forward :74-81) and the backward of its mse term with
 // dL/dQ_j = 1: every per-row gradient vector of the MLP backward is linear in the row's
@@ -3653,7 +3438,7 @@ static int wide_head_bytes(int kind, const GemmProb& p) {
     const int ad = p.exi[policy_head::kAd], ldw4 = p.exi[policy_head::kLdw4];
     if (ad <= kHeadRegs || ldw4 % 4 || !al16(p.ex[policy_head::kW4])) return 0;
     n = (size_t)ad * ldw4;
-  } else if (kind == kRowActorHeadBwd) {
+  } else if (kind == kRowActorHeadBwd || kind == kRowActorHeadBwdBc) {   // (the BC kind keeps the plain kind's slots)
     namespace ab = actor_head_bwd;
     const int ad = p.exi[ab::kAd], ldw4 = p.exi[ab::kLdw4], ld1 = p.exi[ab::kLdW1T];
     if (ad <= kHeadRegs || !p.ex[ab::kW1T] || ld1 % 4 || ldw4 % 4 || !al16(p.ex[ab::kW1T]) || !al16(p.ex[ab::kW4]))
@@ -3666,6 +3451,7 @@ static int wide_head_bytes(int kind, const GemmProb& p) {
 // Marks the wide problems (GemmProb::tile_begin, read by the row kernels as the wide flag) of a
 // row table whose problems [0, n1) are of kind k1 and the rest of kind k2; returns the LDS bytes.
 // TD3_WIDE_HEADS=0 keeps the block-by-block requests (read per launch: the bit-identity test flips it)
+static thread_local int g_last_row_lds = -1;   // td3_debug_row_lds
 static int mark_wide(GemmTable& d, int k1, int k2, int n1) {
   const char* e = getenv("TD3_WIDE_HEADS");
   const bool on = !e || atoi(e) != 0;
@@ -3675,8 +3461,10 @@ static int mark_wide(GemmTable& d, int k1, int k2, int n1) {
     d.p[i].tile_begin = b > 0;
     lds = std::max(lds, b);
   }
+  g_last_row_lds = lds;
   return lds;
 }
+int last_row_lds() { return g_last_row_lds; }
 
 template <bool NORM>
 static int launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) {
@@ -3693,6 +3481,8 @@ static int launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) {
       if (lds) hipLaunchKernelGGL((row_kernel<kRowActorHeadBwd, NORM, kWideRows>), wgrid, wblock, lds, s, Bp, d);
       else hipLaunchKernelGGL((row_kernel<kRowActorHeadBwd, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d);
       break;
+    case kRowActorHeadBwdBc:   // its kernels live in bc.hip, a code object of their own
+      return launch_rows_bc(d, lds, Bp, s);
     case kRowCriticLossP:
       hipLaunchKernelGGL((row_kernel<kRowCriticLossP, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d);
       break;

@@ -159,6 +159,11 @@ struct Plan {
   // the rows' |TD error| and the injected mass fractions of a prioritized draw
   float *per_w = nullptr, *per_td = nullptr, *per_u = nullptr;
   bool per_w_dirty = false;
+  // TD3+BC (td3_set_bc; null / false in a plan built with it off): the live rows' sum over the action
+  // of (pi - a)^2 [Bp], and (lambda, mean |Q1(s, pi)|) of the last actor step, written by its
+  // actor_head_bwd stage
+  float *bc_se = nullptr, *bc_lam = nullptr;
+  bool bc = false;
   // particles: each critic's rows' sum over the Q outputs of |Q_j - y| (critic_loss_p::kTd), [J][Bp];
   // the prioritized step combines them into per_td (per_td_combine_kernel)
   float* per_tdj = nullptr;
@@ -366,6 +371,10 @@ struct td3_handle {
   std::vector<std::string> stage_names;
   std::vector<std::string> stage_kernels;
   std::unique_ptr<td3::TrainLog> log;         // td3_log_enable; null: steps queue nothing for it
+  // TD3+BC (td3_set_bc): the weight alpha (0: off) and total_it of the last actor step taken with it in
+  // the current plan (0: none; the plan holds that step's lambda and row errors)
+  double bc_alpha = 0.0;
+  int64_t bc_step = 0;
 };
 
 namespace td3 {
@@ -436,6 +445,10 @@ int bind_ring(td3_handle* h, Ring* r);
 int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* stats, bool prioritized = false);
 enum RingUser : int { kLearnerStep = 0, kReplicaStep = 1 };
 int check_ring(const td3_handle* h, const Ring* r, RingUser what);
+// the host's note of a step just queued with the BC actor phase (td3_bc_info's `step`); total_it is the step's
+inline void note_bc_step(td3_handle* h, int actor_phase) {
+  if (actor_phase && h->plan && h->plan->bc) h->bc_step = h->total_it;
+}
 // ---- trainlog.hip
 int log_step(td3_handle* h, int actor_phase, bool prioritized, hipStream_t s);
 void destroy_train_log(td3_handle* h);

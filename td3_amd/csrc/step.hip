@@ -103,6 +103,7 @@ static int build_step(td3_handle* h, int B) {
   const int sd = h->sd, ad = h->ad;
   P->ld_sa = pad32(sd + ad);
   P->fuse_gather = 2 * sd + ad + 2 <= 128;
+  P->bc = h->bc_alpha > 0.0;                  // TD3+BC (td3_set_bc): the BC form of actor_head_bwd
   const NetL& an = h->actor.nets[0];
   const NetL& q1 = h->critic.nets[0];
   const NetL& q2 = h->critic.nets[1];
@@ -126,6 +127,10 @@ static int build_step(td3_handle* h, int B) {
     P->per_td = S.take(Bp);
     P->per_u = S.take(Bp);
     P->W1aT = S.take((size_t)ad * q1.lin[0].Np);
+    if (P->bc) {
+      P->bc_se = S.take(Bp);
+      P->bc_lam = S.take(4);
+    }
     alloc_eval(S, an, Bp, P->X_S2A, P->ld_sa, false, norm, false, P->TA);
     alloc_eval(S, q1, Bp, P->X_SA, P->ld_sa, true, norm, true, P->Q[0]);
     alloc_eval(S, q2, Bp, P->X_SA, P->ld_sa, true, norm, true, P->Q[1]);
@@ -299,8 +304,20 @@ static int build_step(td3_handle* h, int B) {
         p.exi[ab::kLd0] = q1.lin[0].Np;
         p.exi[ab::kLdw1] = q1.lin[0].Kp;
         set_actor_bwd(p, Pa, an, P->A, sd, ad, ma);
+        if (P->bc) {
+          // the stored action: the [s | a] rows every input path leaves in X_SA (the twin's dW input;
+          // the ring-fused first layer writes them as the twin problem's row copy)
+          namespace bc = actor_head_bwd_bc;
+          p.ex[bc::kQv] = P->AQ.Qv;
+          p.ex[bc::kAct] = P->X_SA;
+          p.ex[bc::kRowSe] = P->bc_se;
+          p.ex[bc::kLam] = P->bc_lam;
+          p.exi[bc::kLdAct] = P->ld_sa;
+          p.exf[bc::kAlpha] = (float)h->bc_alpha;
+          p.exf[bc::kBcScale] = (float)(2.0 / ((double)B * ad));
+        }
         std::vector<GemmProb> v = {p};
-        TD3_RC(push_row_stage(st, v, kRowActorHeadBwd, Bp, "actor_head_bwd"));
+        TD3_RC(push_row_stage(st, v, P->bc ? kRowActorHeadBwdBc : kRowActorHeadBwd, Bp, "actor_head_bwd"));
       }
       std::vector<BwdItem> ab = {{&an, Pa, &P->A, true}};
       BwdOpts abo;
@@ -844,6 +861,7 @@ static int run_body(td3_handle* h, int actor_phase, int inj, hipStream_t s, Ring
 
 int build_plan(td3_handle* h, int B) {
   const bool was_sharded = h->dp_sharded && h->nranks > 1;
+  h->bc_step = 0;                             // the last BC step's lambda / row errors go with the plan
   h->dp_sharded = false;                      // set again by add_dw_stage when it shards
   // the profiled stage list lives in the plan being replaced
   h->last_body = nullptr;
@@ -910,6 +928,7 @@ int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* s
   }
   // the training log's launch: behind the body (and a prioritized step's write-back), ahead of the sync
   if (h->log && h->total_it % h->log->every == 0) TD3_RC(log_step(h, actor_phase, prioritized, s));
+  note_bc_step(h, actor_phase);
   if (!stats) return 0;
   Plan* P = h->plan.get();
   TD3_HIP(hipStreamSynchronize(s));

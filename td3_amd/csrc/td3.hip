@@ -450,6 +450,46 @@ int td3_get_adam(const td3_handle* h, int group, double out[4]) {
   return 0;
 }
 
+// TD3+BC (include/td3.h, "TD3+BC"): alpha is a launch argument of the actor_head_bwd stage, so a new
+// value rebuilds the plan (build_step reads h->bc_alpha) and with it the captured graphs.
+int td3_set_bc(td3_handle* h, double alpha) {
+  TD3_ARG(std::isfinite(alpha) && alpha >= 0.0, "alpha must be finite and >= 0");
+  TD3_ARG(h != nullptr, "null handle");
+  TD3_ARG(!h->particles, "td3_set_bc on a particle learner (the particle learner has no BC step yet)");
+  TD3_ARG(!h->comm && !h->local,
+          "td3_set_bc on a data-parallel handle (comm group attached): lambda would need the global batch's mean");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_HIP(hipStreamSynchronize(h->stream));
+  if (h->bc_alpha == alpha) return 0;
+  h->bc_alpha = alpha;
+  h->bc_step = 0;
+  if (h->plan) TD3_RC(build_plan(h, h->plan->B));
+  return 0;
+}
+
+int td3_bc_info(td3_handle* h, td3_bc_info_t* info) {
+  TD3_ARG(info != nullptr, "null info");
+  TD3_ARG(h != nullptr, "null handle");
+  *info = td3_bc_info_t{};
+  info->enabled = h->bc_alpha > 0.0 ? 1 : 0;
+  info->alpha = h->bc_alpha;
+  const Plan* P = h->plan.get();
+  if (!h->bc_step || !P || !P->bc) return 0;
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_HIP(hipDeviceSynchronize());              // the last step may sit on a caller's stream
+  float lam[2];
+  std::vector<float> se((size_t)P->B);
+  TD3_HIP(hipMemcpy(lam, P->bc_lam, sizeof(lam), hipMemcpyDeviceToHost));
+  TD3_HIP(hipMemcpy(se.data(), P->bc_se, se.size() * 4, hipMemcpyDeviceToHost));
+  double sum = 0;
+  for (float v : se) sum += (double)v;
+  info->step = h->bc_step;
+  info->lambda = lam[0];
+  info->q_abs_mean = lam[1];
+  info->bc_loss = sum / ((double)P->B * h->ad);
+  return 0;
+}
+
 // The host waits by polling an event recorded behind the queued steps: a blocking stream sync sleeps
 // on an interrupt once the wait grows long, and its wake-up added tens of us to the end of every
 // burst of steps (e.g. the 20-step timed runs of the driver's bench command).  One event record (a
