@@ -6,13 +6,13 @@
 namespace td3 {
 
 template <bool NORM, int RW = kRowWaves>
-__global__ __launch_bounds__(64 * RW) void row_bc_kernel(int Bp, GemmTable tab) {   // as row_kernel (kernels.hip)
+__global__ __launch_bounds__(64 * RW) void row_bc_kernel(int Bp, GemmTable tab) {   // as row_kernel (kernels_rows.h)
   const GemmProb& P = tab.p[blockIdx.y];
   const RowCtx c{(int)(blockIdx.x * RW + (threadIdx.x >> 6)), (int)(threadIdx.x & 63), Bp};
   row_actor_head_bwd<NORM, RW, true>(P, c);
 }
 
-// d: the table with its wide problems marked, lds: the wide stage's bytes (launch_rows, kernels.hip)
+// d: the table with its wide problems marked, lds: the wide stage's bytes (launch_rows, kernels_launch.h)
 int launch_rows_bc(const GemmTable& d, int lds, int Bp, hipStream_t s) {
   const dim3 grid(Bp / kRowWaves, d.nprob), wgrid(Bp / kWideRows, d.nprob);
   if (d.p[0].norm) {

@@ -601,7 +601,7 @@ struct DwSplit {
 };
 int launch_dw_split(const DwArgs& a, const DwSplit& k, hipStream_t s);
 
-// ------------------------------------------------------------------ launchers (kernels.hip)
+// ------------------------------------------------------------------ launchers (kernels_launch.h)
 // launch_gemm's bump_actor: 0 bumps total_it / critic_step, 1 also actor_step, kBumpActorOnly only
 // actor_step (TD3_particles._actor_learn outside a train step: the actor's Adam step, no total_it)
 constexpr int kBumpActorOnly = 2;

@@ -413,7 +413,7 @@ def test_overlapped_allreduce_schedule_single_rank(monkeypatch):
 @pytest.mark.parametrize("sd,ad", [(24, 4), (29, 3)])
 def test_layer0_widths_teacher_forced(sd, ad):
     """Network inputs of 25..32 columns: the fused layer 0 runs its 16-MFMA K layout (inputs of
-    <= 24 columns, every golden config, use 12 MFMAs per tile, kernels.hip l0_koff)."""
+    <= 24 columns, every golden config, use 12 MFMAs per tile, kernels_prologues.h l0_koff)."""
     S = featured_setup_dims(sd, ad)
     pol, rb = _make(S)
     L = orc.Learner(S["actor"], S["critic"], **S["kw"])

@@ -14,7 +14,7 @@ learner then runs the same step from the same state with those indices and that 
 (``td3_profile_stages`` / ``td3_stage_kernel``; prologue numbers in the names: 0 = kProCopy,
 3 = kProGather, 5 = kProL0G).
 
-First-layer instantiations of the ring-sampled step (kernels.hip) and the cases that run them.
+First-layer instantiations of the ring-sampled step (kernels_launch.h) and the cases that run them.
 The planner (stages.hip gemm_wn, can_fuse_l0, l0r16_config) picks per phase: a policy step has a
 fourth network (the online actor) in the launch, so hc_none / hc_wn / inj_noise (B = 256) run
 l0r16 on the critic-only step and the 32-row GEMM on the policy step.

@@ -1,5 +1,5 @@
 """Wide policy / actor heads (action width > 8; Humanoid: 17) stage their weight rows in LDS once per
-workgroup (kernels.hip wide_stage, row kernels launched with kWideRows rows per workgroup) instead of
+workgroup (row_actor.h wide_stage, row kernels launched with kWideRows rows per workgroup) instead of
 requesting them block by block.  The staged rows are the same values, used in the same order, so the
 parameters after Philox steps (critic-only and policy steps) are bit-identical to the block-by-block
 path (TD3_WIDE_HEADS=0), for both LayerNorm settings and for widths that leave a ragged last block."""

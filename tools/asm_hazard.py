@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Check the gfx950 ISA of the kernels for hand-placed asynchronous loads into registers.
 
-Round 3's `row_policy_head` (kernels.hip) issued the step-counter load as inline asm with a VGPR
+Round 3's `row_policy_head` (kernels_rows.h) issued the step-counter load as inline asm with a VGPR
 output and waited for it (`s_waitcnt vmcnt(0)`) only where the Philox noise is drawn (round 4: an
 ordinary divergent load the compiler tracks; `asm_vgpr_loads` must find none).  The compiler treats the
 asm output as defined at the asm statement, so it is free to copy or spill that register before the

@@ -3,7 +3,8 @@
 #   tools/build_exp.sh NAME "-DSOME_KNOB=1 ..."   ->  tools/exp/libtd3hip_NAME.so
 # Knockout builds (-DTD3_KO_* / -DTD3_X_*: wrong results, timing only) compile kernels.hip with
 # tools/exp_patches/knockout.patch applied to a scratch copy: the product source holds no
-# wrong-result blocks.
+# wrong-result blocks.  (knockout.patch is a record against kernels.hip as one file, before its split into the
+# csrc/kernels_*.h parts; it no longer applies.)
 set -e
 cd "$(dirname "$0")/.."
 out=${EXP_DIR:-tools/exp}; mkdir -p $out

@@ -1,6 +1,6 @@
 // Micro-benchmark (GPU box): where a split-K dW step's time goes.  One workgroup per CU runs
 // `steps` 64-row steps of one 128x128 (or 64x64) dW tile, dW = G^T U over G, U [rows][512] fp32,
-// the staging and MFMA loop of td3_amd/csrc/kernels.hip dwsk_matrix128 / dwsk_matrix, in modes
+// the staging and MFMA loop of td3_amd/csrc/kernels_dwsk.h dwsk_matrix128 / dwsk_matrix, in modes
 //   0 full (LDS-DMA double buffer + MFMA from LDS)   1 MFMA from LDS only (no DMA)
 //   2 DMA + barriers only (no MFMA)                   3 MFMA from registers only
 // Prints us per step per CU and the MFMA fraction of the f32 peak.

@@ -1,5 +1,5 @@
 // Micro-benchmark (GPU box): how fast a GEMM stage's weight fragments reach the registers, by the
-// per-lane pattern of the loads.  The F_fwd01 shape of l0r16_kernel<5, 2> (td3_amd/csrc/kernels.hip):
+// per-lane pattern of the loads.  The F_fwd01 shape of l0r16_kernel<5, 2> (td3_amd/csrc/kernels_l0r16.h):
 // 240 workgroups of 10 waves, 3 networks x 5 column tiles of 80 x 16 row tiles; wave (c, kq) loads
 // rows n0 + 16c + (lane & 15) of W [400][512] over its half of K in 32-deep chunks (160 KB per
 // workgroup, 2.4 MB distinct), as the MFMA fragments of v_mfma_f32_16x16x4_f32 need them.
