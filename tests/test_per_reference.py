@@ -4,6 +4,7 @@ import copy
 import numpy as np
 import pytest
 
+import bc_reference as bcr
 import per_reference as per
 from helpers import featured_setup, gen, orc
 
@@ -70,3 +71,102 @@ def test_reference_draw_meets_the_chi_square_bound(rows, batches, bound):
         assert d == dof and chi2 < bound, (seed, chi2)
     uniform = np.random.RandomState(9).randint(0, rows, size=batches * B)
     assert per.chi_square(np.bincount(uniform, minlength=rows).astype(np.float64), p)[0] > 10 * bound
+
+
+# ---------------------------------------------------------------- the edge cases (per.EDGES)
+_EDGE_IDS = [c["name"] for c in per.EDGES]
+_DUPLICATES = ("b257", "dw64", "dwsk", "hum1024")
+
+
+def test_step_case_is_unchanged():
+    """The inputs of the two golden cases' callers, as they were before EDGES existed."""
+    S, p, u, noise = per.step_case("hc_layer", 1)
+    assert (S["B"], p.shape, u.shape, noise.shape) == (256, (gen.BUFFER_ROWS,), (256,), (256, 6))
+    assert p[:8].tolist() == [8.0, 9.0, 1.0, 4.0, 14.0, 6.0, 15.0, 8.0]
+    assert [float(x).hex() for x in u[:8]] == [
+        "0x1.4401aa0000000p-2", "0x1.abdd860000000p-2", "0x1.d25ec20000000p-3", "0x1.c8ee080000000p-1",
+        "0x1.ae570e0000000p-3", "0x1.da84440000000p-1", "0x1.beedd20000000p-1", "0x1.ea686c0000000p-2"]
+
+
+def test_edge_table():
+    assert _EDGE_IDS == ["b1", "b33", "b257", "dw64", "dwsk", "none", "wn", "hum", "hum1024", "rec139", "a32",
+                         "a1", "in512", "odd", "part", "bc17", "bc1000"]
+    by = {c["name"]: c for c in per.EDGES}
+    assert [(n, by[n]["beta"]) for n in _EDGE_IDS if by[n]["beta"] != 1.0] == [("b257", 0.4), ("hum1024", 0.4)]
+    assert [(n, per.edge_fill(by[n])) for n in _EDGE_IDS if "fill" in by[n]] == [("in512", 300), ("part", 300)]
+    assert [(n, by[n]["bc_alpha"]) for n in _EDGE_IDS if "bc_alpha" in by[n]] == [("bc17", 2.5), ("bc1000", 2.5)]
+    assert (by["odd"]["actor_arch"], by["odd"]["q_arch"]) == ((64, 48, 40), (96, 72, 33))
+    assert max(c["B"] for c in per.EDGES) == 1024
+
+
+def _edge_reference_step(case, L, batch, noise, w):
+    """The reference step the GPU test compares with: weighted, with the BC actor loss in the bc* cases;
+    ``w`` None: the same step without weights."""
+    if case.get("bc_alpha"):
+        return bcr.bc_featured_step(L, batch, noise, case["bc_alpha"], w=w)
+    if w is None:
+        return orc.featured_train_step(L, batch, noise)
+    return per.weighted_featured_step(L, batch, noise, w)
+
+
+@pytest.mark.parametrize("case", per.EDGES, ids=_EDGE_IDS)
+def test_edge_case_inputs(case):
+    """The conditions the GPU test (tests/test_gpu_prioritized_edges.py) leans on, for the same two steps
+    from the same chain of oracle states: the draw is exact and stays inside the filled rows, the
+    weights spread, rows repeat where the case is there for that, both BC terms carry weight, and the
+    critic's exp_avg of a step that ignored the weights is more than 100x MOMENT_TOL away, tensor by tensor.
+    b1 is exempt from the spread and the separation: its one weight is 1 and both steps are the same."""
+    S = per.edge_setup(case)
+    fill, B, beta = S["fill"], S["B"], case["beta"]
+    assert S["buf"].size == fill and (S["sd"], S["ad"], S["ma"], S["norm"]) == \
+        (case["sd"], case["ad"], case["max_action"], case["norm"])
+    Lw = orc.Learner(S["actor"], S["critic"], **S["kw"])
+    for step in (1, 2):
+        p, u, noise = per.edge_step(case, S, step)
+        assert p.shape == (fill,) and u.shape == (B,) and noise.shape == (B, S["ad"])
+        assert p.min() >= 1 and p.max() <= 15 and (p == np.round(p)).all()
+        assert float(np.float32(p.sum())) == p.astype(np.float64).sum()        # exact prefix sums
+        assert ((u * np.float32(p.sum())).astype(np.float32) < p.sum()).all()
+        idx = per.draw(p, u)
+        assert idx.min() >= 0 and idx.max() < fill
+        w = per.weights(p, idx, fill, beta)
+        assert w.max() == 1.0
+        if B == 1:
+            assert w[0] == 1.0
+        else:
+            assert w.min() <= (0.2 if beta == 1.0 else 0.5), w.min()
+        if case["name"] in _DUPLICATES:
+            assert B - np.unique(idx).size >= 1
+        Lu = copy.deepcopy(Lw)
+        batch = S["buf"].gather(idx)
+        rec = _edge_reference_step(case, Lw, batch, noise, w)
+        _edge_reference_step(case, Lu, batch, noise, None)
+        assert ("actor_loss" in rec) == (step == 2)
+        if B > 1:
+            for k in Lw.critic_m:
+                assert _rel_to_max(Lu.critic_m[k], Lw.critic_m[k]) > 100 * per.MOMENT_TOL, (step, k)
+        if case.get("bc_alpha") and step == 2:
+            sq, sb = bcr.term_shares(rec)
+            assert sq >= bcr.MIN_SHARE and sb >= bcr.MIN_SHARE, (sq, sb)
+
+
+@pytest.mark.parametrize("name", ["wn", "odd"])
+def test_unit_weights_reproduce_the_oracle_step_at_edges(name):
+    """As test_unit_weights_reproduce_the_oracle_step, without LayerNorm (weight norm's g / v gradients)
+    and at the custom widths."""
+    case = {c["name"]: c for c in per.EDGES}[name]
+    S = per.edge_setup(case)
+    La = orc.Learner(S["actor"], S["critic"], **S["kw"])
+    Lb = copy.deepcopy(La)
+    for step in (1, 2):
+        p, u, noise = per.edge_step(case, S, step)
+        batch = S["buf"].gather(per.draw(p, u))
+        ra = per.weighted_featured_step(La, batch, noise, np.ones(S["B"], np.float32))
+        rb = orc.featured_train_step(Lb, batch, noise)
+        for k in ("y", "q1", "q2", "next_action"):
+            np.testing.assert_array_equal(ra[k], rb[k])
+        assert ra["critic_loss"] == rb["critic_loss"] and ra.get("actor_loss") == rb.get("actor_loss")
+        assert ("actor_loss" in ra) == (step == 2)
+        for grp in ("actor", "critic", "actor_target", "critic_target", "actor_m", "actor_v", "critic_m", "critic_v"):
+            for k, v in getattr(La, grp).items():
+                np.testing.assert_array_equal(v, getattr(Lb, grp)[k], err_msg=f"{grp}/{k}")
