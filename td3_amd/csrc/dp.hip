@@ -1,5 +1,5 @@
-// The data-parallel seam: the schedule choices read at plan build, the sharded optimizer state,
-// the RCCL communicator and the in-process replica group (td3_comm_*, td3_train_step_local).
+// The data-parallel seam: the schedule choices read at plan build and the three schedules they choose among,
+// the sharded optimizer state, the RCCL communicator and the replica group (td3_comm_*, td3_train_step_local).
 #include "learner.h"
 
 namespace td3 {
@@ -22,11 +22,204 @@ bool dp_overlap(const td3_handle* h) {
 // RCCL peers has priced the sharded form's second collective call; 1: sharded for more than one
 // rank; 2: sharded always (tests, pricing).  Weight normalization and the bucketed schedule keep
 // the all-reduce.  Read at plan build.
-bool dp_shard(const td3_handle* h) {
+static bool dp_shard(const td3_handle* h) {
   const int m = env_int("TD3_DP_SHARD", 0);
   return m == 2 || (m == 1 && h->nranks > 1);
 }
-int64_t shard_slice(const Group& g, int nranks) { return ((g.size + 4 * nranks - 1) / (4 * nranks)) * 4; }
+static int64_t shard_slice(const Group& g, int nranks) { return ((g.size + 4 * nranks - 1) / (4 * nranks)) * 4; }
+
+// An RCCL call's result as the library's: 0, or -2 with the error text set
+static int nccl_rc(ncclResult_t r, const char* call) {
+  if (r == ncclSuccess) return 0;
+  set_error("%s: %s", call, ncclGetErrorString(r));
+  return -2;
+}
+
+// The exchange stage of the group `adam` steps: `rccl` makes the RCCL calls.  A td3_comm_init_local
+// replica refuses to launch it: the seam runs its fixed-order sum and Stage::after instead.
+using Launch = std::function<int(hipStream_t)>;
+static Stage collective_stage(const td3_handle* h, const std::string& name, const AdamArgs& adam, Launch rccl) {
+  if (h->local)
+    rccl = [](hipStream_t) {
+      set_error("a td3_comm_init_local replica steps through td3_train_step_local only");
+      return -1;
+    };
+  Stage x{name, rccl, 0, "rccl"};
+  x.collective = adam.which == 1 ? 0 : 1;         // AdamArgs::which 1 = actor -> group 0, 0 = critic -> group 1
+  return x;
+}
+
+// The flat optimizer's image map of a group's forward weights (P4 null when the plan being built does
+// not use the images); `base`: the arena offset of the range it updates
+static int w4_map(const td3_handle* h, const Group& g, int64_t base, W4Map* out) {
+  W4Map w{};
+  if (h->w4_build) {
+    w.P4 = g.P4;
+    w.T4 = g.T4;
+    w.base = base;
+    for (const NetL& n : g.nets)
+      for (int l = 0; l < 3; ++l) {
+        TD3_ARG(w.nmat < 8, "internal: too many matrices for the flat optimizer's image map");
+        w.off[w.nmat] = n.lin[l].offW;
+        w.Np[w.nmat] = n.lin[l].Np;
+        w.Kp[w.nmat] = n.lin[l].Kp;
+        ++w.nmat;
+      }
+  }
+  *out = w;
+  return 0;
+}
+
+// The flat optimizer step of [off, off + n) of a group's arena as a launch: the AdamArgs moved to the range
+// and, with `images`, the image map based there (the sharded step leaves the images to the stage behind it)
+static int flat_adam(const td3_handle* h, const Group& g, AdamArgs a, int64_t off, int64_t n, int polyak,
+                     bool images, Launch* out) {
+  a.P += off; a.G += off; a.M += off; a.V += off; a.T += off;
+  W4Map wm{};
+  if (images) TD3_RC(w4_map(h, g, off, &wm));
+  *out = [=](hipStream_t s) { return launch_adam_flat(a, n, polyak, s, images ? &wm : nullptr); };
+  return 0;
+}
+
+// The overlapped schedule for a twin critic whose dW is split-K: one bucket per network
+// in arena order.  Stages: dW_0 (gradient only; then an event on the step stream), dW_1 (then a
+// second event), bucket 0's all-reduce + Adam (+ Polyak) on the comm stream behind the first event,
+// bucket 1's on the comm stream behind the second (one RCCL stream per communicator: ADVICE r04),
+// then the join (the step stream waits for bucket 1's Adam).  Bucket 0's exchange runs under dW_1;
+// dW_1 is enqueued before the host makes bucket 0's RCCL call.  The in-process seam runs the same
+// buckets: a fixed-order sum of the range, then the bucket's optimizer step (Stage::after), on its
+// one stream.  dp_buckets: whether a data-parallel group's dW stage takes this schedule.
+bool dp_buckets(const td3_handle* h, const Group& g, const std::vector<BwdItem>& items, const DwOpts& o,
+                const DwWork& w) {
+  return w.split && g.wn.nlin == 0 && o.enc_nwg == 0 && items.size() == 2 && dp_overlap(h);
+}
+int add_dp_overlapped(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
+                      const char* tag, const DwOpts& o, const DwWork& w) {
+  td3_handle* h = c.h;
+  const bool local = h->local != nullptr;
+  ncclComm_t comm = h->comm;
+  hipStream_t cs = h->comm_stream;
+  hipEvent_t done = h->comm_done;
+  TD3_ARG(local || (cs && h->comm_ev && h->comm_ev1 && done), "internal: data-parallel handle without a comm stream");
+  AdamArgs adam = w.a.adam;
+  adam.grad_scale = 1.0f / (float)h->nranks;      // the ranks' mean
+  auto begin = [](const NetL& n) { return n.enc_off >= 0 ? n.enc_off : n.lin[0].offW; };
+  std::vector<Stage> exch;                        // bucket b's exchange stage
+  for (size_t b = 0; b < items.size(); ++b) {
+    const bool first = b == 0;
+    hipEvent_t ev = first ? h->comm_ev : h->comm_ev1;
+    TD3_RC(push_dw_stage(c, st, dw_bucket(w, items, b), o.slab, std::string(tag) + "_dw_" + std::to_string(b)));
+    if (!local) {
+      Launch dw = st.back().run;
+      st.back().run = [=](hipStream_t s) {
+        TD3_RC(dw(s));
+        TD3_HIP(hipEventRecord(ev, s));
+        return 0;
+      };
+    }
+    const int64_t off = begin(*items[b].net);
+    const int64_t end = b + 1 < items.size() ? begin(*items[b + 1].net) : g.size;
+    TD3_ARG(off >= 0 && end > off && end <= g.size, "internal: bucket range");
+    const int64_t nb = end - off;
+    Launch step;
+    TD3_RC(flat_adam(h, g, adam, off, nb, o.polyak ? 1 : 0, true, &step));
+    float* Gb = g.G + off;
+    Stage x = collective_stage(h, std::string(tag) + "_" + std::to_string(b) + "_allreduce", adam, [=](hipStream_t) {
+      TD3_HIP(hipStreamWaitEvent(cs, ev, 0));
+      TD3_RC(nccl_rc(ncclAllReduce(Gb, Gb, (size_t)nb, ncclFloat, ncclSum, comm, cs), "ncclAllReduce"));
+      TD3_RC(step(cs));
+      if (!first) TD3_HIP(hipEventRecord(done, cs));
+      return 0;
+    });
+    x.coll_off = off; x.coll_n = nb;
+    x.after = step;
+    exch.push_back(x);
+  }
+  for (auto& x : exch) st.push_back(x);          // dW_0, dW_1, exchange 0, exchange 1
+  st.push_back({std::string(tag) + "_join",
+                [=](hipStream_t s) {
+                  if (local) return 0;            // the seam ran the buckets on its stream
+                  TD3_HIP(hipStreamWaitEvent(s, done, 0));
+                  return 0;
+                },
+                0, "(stream join)"});
+  return 0;
+}
+
+// The sharded data-parallel step updates 1/N of P per rank and all-gathers P: the images are
+// repacked by a stage of their own behind it (the dW kernels run gradient-only in data-parallel
+// plans; the replicated flat optimizer of the all-reduce schedules writes the images itself)
+static int push_w4_pack(td3_handle* h, std::vector<Stage>& st, const Group& g, bool polyak, const char* tag) {
+  if (!h->w4_build) return 0;
+  W4PackArgs a;
+  TD3_RC(w4_pack_args(g, polyak, &a));
+  st.push_back({std::string(tag) + "_w4", [=](hipStream_t s) { return launch_w4_pack(a, s); }, 0,
+                "td3::w4_pack_kernel"});
+  return 0;
+}
+
+// Sharded optimizer step (ZeRO-1 form): the summed gradient reaches only this
+// rank's slice (ncclReduceScatter, in place), Adam runs on that slice alone (the moments of the
+// other slices live on their owners), ncclAllGather brings every rank the updated parameters,
+// then Polyak runs replicated over the whole arena (the same inputs on every rank: the replicas
+// stay bit-identical, each element computed once).  Same bytes on the links as the all-reduce,
+// one extra collective launch, 1/N of the Adam pass.
+static int add_dp_sharded(td3_handle* h, std::vector<Stage>& st, Group& g, const AdamArgs& adam, bool polyak,
+                          const char* tag) {
+  const int N = h->nranks, R = h->rank;
+  const int64_t slice = shard_slice(g, N);
+  TD3_ARG(N * slice <= g.cap, "internal: shard slices past the arena");
+  h->dp_sharded = true;
+  ncclComm_t comm = h->comm;
+  float *G = g.G, *Pp = g.P, *Tp = g.T;
+  Launch step;
+  TD3_RC(flat_adam(h, g, adam, R * slice, slice, 0, false, &step));
+  Stage x = collective_stage(h, std::string(tag) + "_rs_adam_ag", adam, [=](hipStream_t s) {
+    TD3_RC(nccl_rc(ncclReduceScatter(G, G + R * slice, (size_t)slice, ncclFloat, ncclSum, comm, s), "ncclReduceScatter"));
+    TD3_RC(step(s));
+    return nccl_rc(ncclAllGather(Pp + R * slice, Pp, (size_t)slice, ncclFloat, comm, s), "ncclAllGather");
+  });
+  x.coll_slice = slice; x.after = step;
+  st.push_back(x);
+  const int64_t n = g.size;
+  const float tau = (float)h->cfg.tau;
+  if (polyak && h->w4_build) {          // Polyak and both images in one pass over the gathered arena
+    W4Map wm;
+    TD3_RC(w4_map(h, g, 0, &wm));
+    st.push_back({std::string(tag) + "_polyak", [=](hipStream_t s) { return launch_polyak_w4(Tp, Pp, n, tau, wm, s); },
+                  0, "td3::polyak_w4_kernel"});
+    return 0;
+  }
+  if (polyak)
+    st.push_back({std::string(tag) + "_polyak", [=](hipStream_t s) { return launch_polyak_flat(Tp, Pp, n, tau, s); },
+                  0, "td3::polyak_flat_kernel"});
+  return push_w4_pack(h, st, g, false, tag);
+}
+
+// All-reduce of the group's whole gradient arena, then the replicated optimizer step: the flat Adam
+// (+ Polyak, + images), or wn_kernel under weight normalization
+static int add_dp_allreduce(td3_handle* h, std::vector<Stage>& st, Group& g, const AdamArgs& adam, bool polyak,
+                            const char* tag) {
+  ncclComm_t comm = h->comm;
+  float* G = g.G;
+  const int64_t n = g.size;
+  st.push_back(collective_stage(h, std::string(tag) + "_allreduce", adam, [=](hipStream_t s) {
+    return nccl_rc(ncclAllReduce(G, G, (size_t)n, ncclFloat, ncclSum, comm, s), "ncclAllReduce");
+  }));
+  if (g.wn.nlin > 0) return push_wn_stage(st, g, adam, polyak, tag);
+  Launch step;
+  TD3_RC(flat_adam(h, g, adam, 0, n, polyak ? 1 : 0, true, &step));
+  st.push_back({std::string(tag) + "_adam", step, 0, "td3::adam_flat_kernel"});
+  return 0;
+}
+
+// The optimizer tail of a data-parallel group behind its gradient-only dW stage (`adam`: what the
+// fused step would have used).  Weight normalization keeps the all-reduce.
+int add_dp_optimizer(td3_handle* h, std::vector<Stage>& st, Group& g, AdamArgs adam, bool polyak, const char* tag) {
+  adam.grad_scale = 1.0f / (float)h->nranks;      // the ranks' mean
+  if (g.wn.nlin == 0 && dp_shard(h)) return add_dp_sharded(h, st, g, adam, polyak, tag);
+  return add_dp_allreduce(h, st, g, adam, polyak, tag);
+}
 
 // The in-process seam's gather of one moment arena: the slices the other replicas own, copied in
 static int copy_local_moments(td3_handle* h, int which) {
@@ -50,13 +243,8 @@ static int allgather_moments(td3_handle* h) {
   if (h->last_step_stream && h->last_step_stream != h->stream) TD3_HIP(hipStreamSynchronize(h->last_step_stream));
   for (Group* g : {&h->actor, &h->critic}) {
     const int64_t sl = shard_slice(*g, h->nranks);
-    for (float* a : {g->M, g->V}) {
-      ncclResult_t r = ncclAllGather(a + h->rank * sl, a, (size_t)sl, ncclFloat, h->comm, h->stream);
-      if (r != ncclSuccess) {
-        set_error("ncclAllGather: %s", ncclGetErrorString(r));
-        return -2;
-      }
-    }
+    for (float* a : {g->M, g->V})
+      TD3_RC(nccl_rc(ncclAllGather(a + h->rank * sl, a, (size_t)sl, ncclFloat, h->comm, h->stream), "ncclAllGather"));
   }
   TD3_HIP(hipStreamSynchronize(h->stream));
   return 0;
@@ -110,11 +298,7 @@ int td3_dp_gather_optimizer_state(td3_handle* h) {
 int td3_comm_unique_id(unsigned char out[128]) {
   TD3_ARG(out != nullptr, "null argument");
   ncclUniqueId id;
-  ncclResult_t r = ncclGetUniqueId(&id);
-  if (r != ncclSuccess) {
-    set_error("ncclGetUniqueId: %s", ncclGetErrorString(r));
-    return -2;
-  }
+  TD3_RC(nccl_rc(ncclGetUniqueId(&id), "ncclGetUniqueId"));
   static_assert(sizeof(id) == 128, "ncclUniqueId size");
   memcpy(out, &id, 128);
   return 0;
@@ -129,11 +313,7 @@ int td3_comm_init(td3_handle* h, const unsigned char id[128], int nranks, int ra
   ncclUniqueId uid;
   memcpy(&uid, id, 128);
   ncclComm_t c;
-  ncclResult_t r = ncclCommInitRank(&c, nranks, uid, rank);
-  if (r != ncclSuccess) {
-    set_error("ncclCommInitRank: %s", ncclGetErrorString(r));
-    return -2;
-  }
+  TD3_RC(nccl_rc(ncclCommInitRank(&c, nranks, uid, rank), "ncclCommInitRank"));
   if (h->comm) ncclCommDestroy(h->comm);
   h->comm = c;
   h->nranks = nranks;

@@ -348,14 +348,14 @@ struct td3_handle {
   hipStream_t dev_stream = nullptr;
   hipEvent_t dev_ev = nullptr;
   ncclComm_t comm = nullptr;
-  // the overlapped data-parallel schedule (add_dw_stage buckets): the all-reduces and the per-bucket
+  // the overlapped data-parallel schedule (dp.hip add_dp_overlapped): the all-reduces and the per-bucket
   // optimizer steps run on comm_stream, ordered after the bucket's dW by comm_ev (recorded on the step
   // stream) and joined back by comm_done before the next stage that reads the parameters
   hipStream_t comm_stream = nullptr;
   hipEvent_t comm_ev = nullptr, comm_ev1 = nullptr, comm_done = nullptr;
   std::shared_ptr<td3::LocalGroup> local;          // td3_comm_init_local (comm stays null)
   int nranks = 1, rank = 0;
-  bool dp_sharded = false;                    // the plan's optimizer steps are sharded (add_dw_stage)
+  bool dp_sharded = false;                    // the plan's optimizer steps are sharded (add_dp_sharded)
   bool w4_build = false;                      // the plan being built reads / maintains the k-quad images
   int64_t opt_gathered_it = -1;               // total_it of the last td3_dp_gather_optimizer_state
   std::vector<td3::Stage>* last_body = nullptr;
@@ -409,6 +409,15 @@ struct DwOpts {
   const std::vector<const float*>* unit_scale = nullptr;
   SlabRef* slab = nullptr;
 };
+// A dW stage's work (stages.hip make_dw_work): the launch arguments (every problem of the group's
+// networks, the optimizer's view of its arenas), the tile count of the one-tile-per-workgroup kernels,
+// whether the split-K kernels take it, and the roofline's flops and algorithmic bytes.
+struct DwWork {
+  DwArgs a;
+  int blocks;
+  bool split;
+  double flops, bytes;
+};
 // A plan's carving, written once and run twice by carve_scratch (measuring, then on the allocation)
 using CarveFn = std::function<void(Scratch&, IoCarve&)>;
 
@@ -426,12 +435,16 @@ int env_int(const char* name, int dflt);
 bool can_fuse_l0(const std::vector<FwdItem>& items);
 bool w4_eligible(const td3_handle* h, int Bp);
 int ensure_w4(td3_handle* h, hipStream_t s);
+int w4_pack_args(const Group& g, bool with_t, W4PackArgs* out);
 int add_fwd_stages(const StageCtx& c, std::vector<Stage>& st, const std::vector<FwdItem>& items, const char* tag,
                    const FwdOpts& o);
 int add_bwd_stages(const StageCtx& c, std::vector<Stage>& st, const std::vector<BwdItem>& items, const char* tag,
                    const BwdOpts& o);
 int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
                  const char* tag, const DwOpts& o);
+DwWork dw_bucket(const DwWork& w, const std::vector<BwdItem>& items, size_t b);
+int push_dw_stage(const StageCtx& c, std::vector<Stage>& st, const DwWork& w, SlabRef* slab, const std::string& name);
+int push_wn_stage(std::vector<Stage>& st, const Group& g, const AdamArgs& adam, bool polyak, const char* tag);
 int alloc_dw_slab(Plan* P);
 void free_plan_tables(std::vector<void*>& t);
 // ---- step.hip
@@ -456,8 +469,11 @@ void destroy_train_log(td3_handle* h);
 int map_io(ActPlan* A, size_t floats, IoCarve* io);
 // ---- dp.hip
 bool dp_overlap(const td3_handle* h);
-bool dp_shard(const td3_handle* h);
-int64_t shard_slice(const Group& g, int nranks);
+bool dp_buckets(const td3_handle* h, const Group& g, const std::vector<BwdItem>& items, const DwOpts& o,
+                const DwWork& w);
+int add_dp_overlapped(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
+                      const char* tag, const DwOpts& o, const DwWork& w);
+int add_dp_optimizer(td3_handle* h, std::vector<Stage>& st, Group& g, AdamArgs adam, bool polyak, const char* tag);
 int gather_moments_for_rebuild(td3_handle* h);
 int consolidate_moments(td3_handle* h, int which);
 

@@ -307,7 +307,7 @@ static const float* w4_of(const td3_handle* h, const float* base) {
 // (TD3_W4FAKE, timing only): 10.08 k -> 10.95 k steps/s; CB_bwd2+TF_fwd01 14.5 -> 11.9 us, odd
 // F_fwd01 15.5 -> 12.1, even F_fwd01 18.3 -> 15.9, AF_fwd01 9.7 -> 8.1.  The images are maintained by
 // the dW kernels' optimizer epilogues (dw_kernel, dw64 / dw64g, the split-K combine) and, in
-// data-parallel plans (flat Adam after the exchange), by a pack stage behind it (push_w4_pack).
+// data-parallel plans (flat Adam after the exchange), by a pack stage behind it (dp.hip push_w4_pack).
 // Weight normalization (wn_kernel derives W) and the particle learner read the row-major arena.
 // TD3_W4=0 turns them off.
 bool w4_eligible(const td3_handle* h, int Bp) {
@@ -318,7 +318,7 @@ bool w4_eligible(const td3_handle* h, int Bp) {
 
 // The pack of a group's forward weights (layers 0-2: the heads are read by the row kernels) from P
 // (and T) into their images
-static int w4_pack_args(const Group& g, bool with_t, W4PackArgs* out) {
+int w4_pack_args(const Group& g, bool with_t, W4PackArgs* out) {
   W4PackArgs a{};
   a.src[0] = g.P;
   a.dst[0] = g.P4;
@@ -349,39 +349,6 @@ int ensure_w4(td3_handle* h, hipStream_t s) {
     TD3_RC(launch_w4_pack(a, s));
     g->w4_valid = true;
   }
-  return 0;
-}
-
-// The flat optimizer's image map of a group's forward weights (P4 null when the plan being built does
-// not use the images); `base`: the arena offset of the range it updates
-static int w4_map(const td3_handle* h, const Group& g, int64_t base, W4Map* out) {
-  W4Map w{};
-  if (h->w4_build) {
-    w.P4 = g.P4;
-    w.T4 = g.T4;
-    w.base = base;
-    for (const NetL& n : g.nets)
-      for (int l = 0; l < 3; ++l) {
-        TD3_ARG(w.nmat < 8, "internal: too many matrices for the flat optimizer's image map");
-        w.off[w.nmat] = n.lin[l].offW;
-        w.Np[w.nmat] = n.lin[l].Np;
-        w.Kp[w.nmat] = n.lin[l].Kp;
-        ++w.nmat;
-      }
-  }
-  *out = w;
-  return 0;
-}
-
-// The sharded data-parallel step updates 1/N of P per rank and all-gathers P: the images are
-// repacked by a stage of their own behind it (the dW kernels run gradient-only in data-parallel
-// plans; the replicated flat optimizer of the all-reduce schedules writes the images itself)
-static int push_w4_pack(td3_handle* h, std::vector<Stage>& st, const Group& g, bool polyak, const char* tag) {
-  if (!h->w4_build) return 0;
-  W4PackArgs a;
-  TD3_RC(w4_pack_args(g, polyak, &a));
-  st.push_back({std::string(tag) + "_w4", [=](hipStream_t s) { return launch_w4_pack(a, s); }, 0,
-                "td3::w4_pack_kernel"});
   return 0;
 }
 
@@ -760,32 +727,42 @@ static int make_dw_split(td3_handle* h, std::vector<void*>& owned, const DwArgs&
   return 0;
 }
 
-// Weight / bias / LN grads of every layer of `items`, fused with the optimizer.
-// enc (TD3_particles): the encoder partial slabs of `items` (reduced + optimizer in one launch).
-// unit_scale (featured critic): per item, the dense [Bp] row scale g_r of its unit-gradient
+// The optimizer's view of a group's arenas with optimizer `which`'s hyper-parameters
+static AdamArgs group_adam(const td3_handle* h, const Group& g, int which) {
+  AdamArgs a{};
+  a.P = g.P; a.G = g.G; a.M = g.M; a.V = g.V; a.T = g.T;
+  a.ctr = h->d_ctr;
+  a.which = which;
+  a.lr = h->adam[which].lr; a.eps = h->adam[which].eps;
+  a.beta1 = h->adam[which].beta1; a.beta2 = h->adam[which].beta2;
+  a.tau = (float)h->cfg.tau;
+  a.grad_scale = 1.0f;
+  a.P4 = h->w4_build ? g.P4 : nullptr;     // the dW kernels keep the k-quad images current
+  a.T4 = h->w4_build ? g.T4 : nullptr;
+  return a;
+}
+
+// The dW work of `items` (learner.h DwWork): one problem per layer of every network (weight, bias and
+// LayerNorm affine grads), one more for a network's lnorm1 affine, and the roofline's accounting.
+// o.unit_scale (featured critic): per item, the dense [Bp] row scale g_r of its unit-gradient
 // backward rows (layers 0..2 and their LayerNorms; the head's dZ is the true gradient already).
-int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
-                 const char* tag, const DwOpts& o) {
+static int make_dw_work(const StageCtx& c, const Group& g, const std::vector<BwdItem>& items, const DwOpts& o,
+                        DwWork* out) {
   td3_handle* h = c.h;
-  std::vector<void*>& owned = c.owned;
-  const int Bp = c.Bp, which = o.which, enc_nwg = o.enc_nwg;
-  const bool polyak = o.polyak;
-  const std::vector<const float*>* unit_scale = o.unit_scale;
-  SlabRef* slab = o.slab;
+  const int Bp = c.Bp;
   const bool norm = h->cfg.norm == 1;
   // B >= 512: 64x64 weight tiles with LDS-staged operands (dw64_kernel: half the operand
   // traffic, Humanoid C_dw 73 -> 63 us), else 32x32 register tiles (dw_kernel: more, shorter
   // workgroups for the latency-bound small batches)
   const bool tile64 = Bp >= 512;
-  std::vector<DwProb> probs;
-  int blocks = 0;
-  double flops = 0;
+  DwWork w{};
+  DwArgs& a = w.a;
   double dw_operand_bytes = 0, dw_params = 0, dw_weights = 0;
-  TD3_ARG(!unit_scale || unit_scale->size() == items.size(), "internal: one row scale per dW item");
+  TD3_ARG(!o.unit_scale || o.unit_scale->size() == items.size(), "internal: one row scale per dW item");
   for (size_t k = 0; k < items.size(); ++k) {
     const BwdItem& it = items[k];
     const NetL& n = *it.net;
-    const float* usc = unit_scale ? (*unit_scale)[k] : nullptr;
+    const float* usc = o.unit_scale ? (*o.unit_scale)[k] : nullptr;
     for (int l = 0; l < 4; ++l) {
       const LinearL& L = n.lin[l];
       DwProb p{};
@@ -813,15 +790,16 @@ int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std:
       }
       p.kvalid = L.K;                  // layer 0 may read a wider row (the actor's [s | a] input)
       p.ntk = tile64 ? (L.Kp + 63) / 64 : L.Kp / 32;
-      p.tile_begin = blocks;
-      blocks += (tile64 ? (L.Np + 63) / 64 : L.Np / 32) * p.ntk + L.Np / 32;   // matrix, then vector tiles
-      flops += 2.0 * Bp * L.N * L.K;
+      p.tile_begin = w.blocks;
+      w.blocks += (tile64 ? (L.Np + 63) / 64 : L.Np / 32) * p.ntk + L.Np / 32;   // matrix, then vector tiles
+      w.flops += 2.0 * Bp * L.N * L.K;
       // operands once (dZ and U rows; the LayerNorm vector tiles also dU, H and the statistics),
       // then the optimizer's state per parameter (weight, bias, LN affine)
       dw_operand_bytes += 4.0 * Bp * ((double)L.N + L.K) + ((norm && l < 3) ? 4.0 * Bp * (2.0 * L.N + 2.0) : 0.0);
       dw_params += (double)L.N * L.K + L.N + ((norm && l < 3) ? 2.0 * L.N : 0.0);
       dw_weights += (double)L.N * L.K;
-      probs.push_back(p);
+      TD3_ARG(a.nprob < kMaxDwProbs, "too many problems in one dw stage");
+      a.probs[a.nprob++] = p;
     }
     if (n.lnin) {                                   // lnorm1 affine grads (vector tiles only)
       DwProb p{};
@@ -838,272 +816,114 @@ int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std:
       p.stats = it.e->statsIn;
       p.ntk = 0;
       p.kvalid = 0;
-      p.tile_begin = blocks;
-      blocks += p.Np / 32;
-      probs.push_back(p);
+      p.tile_begin = w.blocks;
+      w.blocks += p.Np / 32;
+      TD3_ARG(a.nprob < kMaxDwProbs, "too many problems in one dw stage");
+      a.probs[a.nprob++] = p;
     }
   }
-  TD3_ARG(probs.size() <= (size_t)kMaxDwProbs, "too many problems in one dw stage");
-  DwArgs a{};
-  for (size_t i = 0; i < probs.size(); ++i) a.probs[i] = probs[i];
-  a.nprob = (int)probs.size();
   a.Bp = Bp;
-  a.adam.P = g.P;
-  a.adam.G = g.G;
-  a.adam.M = g.M;
-  a.adam.V = g.V;
-  a.adam.T = g.T;
-  a.adam.ctr = h->d_ctr;
-  a.adam.which = which;
-  a.adam.lr = h->adam[which].lr;
-  a.adam.beta1 = h->adam[which].beta1;
-  a.adam.beta2 = h->adam[which].beta2;
-  a.adam.eps = h->adam[which].eps;
-  a.adam.tau = (float)h->cfg.tau;
-  a.adam.grad_scale = 1.0f;
-  if (h->w4_build) {                       // the dW kernels keep the k-quad images current
-    TD3_ARG(g.P4 && g.T4, "internal: k-quad images not allocated");
-    a.adam.P4 = g.P4;
-    a.adam.T4 = g.T4;
-  }
-  const bool dp = h->comm != nullptr || h->local != nullptr;
-  const bool wn = g.wn.nlin > 0;            // weight normalization: dW -> (dg, dv) in wn_kernel
-  a.mode = (dp || wn) ? kDwGrad : (polyak ? kDwAdamPolyak : kDwAdam);
+  TD3_ARG(!h->w4_build || (g.P4 && g.T4), "internal: k-quad images not allocated");
+  a.adam = group_adam(h, g, o.which);
+  // data parallel and weight normalization (dW -> (dg, dv) in wn_kernel): the gradient only
+  a.mode = (h->comm || h->local || g.wn.nlin > 0) ? kDwGrad : o.polyak ? kDwAdamPolyak : kDwAdam;
   // a launch's algorithmic bytes: gradient-only dW writes 4 B per parameter; the fused Adam reads and
   // writes P, M, V (24 B; the gradient never leaves registers), Polyak reads and writes T (+8 B), and
   // the k-quad images take every updated weight once more (+4 B, +4 B more for T4 on Polyak steps)
-  const double dw_bytes =
-      dw_operand_bytes +
-      (a.mode == kDwGrad ? 4.0 * dw_params
-                         : dw_params * (a.mode == kDwAdamPolyak ? 32.0 : 24.0) +
-                               (h->w4_build ? dw_weights * (a.mode == kDwAdamPolyak ? 8.0 : 4.0) : 0.0));
+  w.bytes = dw_operand_bytes +
+            (a.mode == kDwGrad ? 4.0 * dw_params
+                               : dw_params * (a.mode == kDwAdamPolyak ? 32.0 : 24.0) +
+                                     (h->w4_build ? dw_weights * (a.mode == kDwAdamPolyak ? 8.0 : 4.0) : 0.0));
   a.tile64 = tile64 ? 1 : 0;
-  a.scaled = unit_scale ? 1 : 0;
-  const int tm = dwsk_tile_edge();
-  const bool split = tile64 && Bp % 64 == 0 && TD3_DWSK;
-  if (dp && split && !wn && enc_nwg == 0 && items.size() == 2 && dp_overlap(h)) {
-    // The overlapped data-parallel schedule for a twin critic: one bucket per network
-    // in arena order.  Stages: dW_0 (split-K, gradient only; then an event on the step stream),
-    // dW_1 (then a second event), bucket 0's all-reduce + Adam (+ Polyak) on the comm stream behind
-    // the first event, bucket 1's on the comm stream behind the second (one RCCL stream per
-    // communicator: ADVICE r04), then the join (the step stream waits for bucket 1's Adam).
-    // Bucket 0's exchange runs under dW_1; dW_1 is enqueued before the host makes bucket 0's RCCL
-    // call.  The in-process seam runs the same buckets: a fixed-order sum of the range, then the
-    // bucket's optimizer step (Stage::after), on its one stream.
-    const bool local = h->local != nullptr;
-    ncclComm_t comm = h->comm;
-    hipStream_t cs = h->comm_stream;
-    hipEvent_t ev = h->comm_ev, ev1 = h->comm_ev1, done = h->comm_done;
-    TD3_ARG(local || (cs && ev && ev1 && done), "internal: data-parallel handle without a comm stream");
-    const int pol = polyak ? 1 : 0;
-    const std::string kname = std::string("td3::dwsk_kernel<") + (unit_scale ? "true, " : "false, ") +
-                              (tm == 128 ? "true>" : "false>");
-    int p0 = 0;
-    std::vector<Stage> exch;                        // bucket b's exchange stage
-    for (size_t b = 0; b < items.size(); ++b) {
-      const NetL& n = *items[b].net;
-      const int cnt = 4 + (n.lnin ? 1 : 0);
-      DwArgs ab = a;
-      ab.nprob = cnt;
-      double fb = 0;
-      for (int i = 0; i < cnt; ++i) {
-        ab.probs[i] = a.probs[p0 + i];
-        if (i < 4) fb += 2.0 * Bp * n.lin[i].N * n.lin[i].K;
-      }
-      p0 += cnt;
-      DwSplit kb{};
-      TD3_RC(make_dw_split(h, owned, ab, slab, kb));
-      const bool first = b == 0;
-      const std::string bn = std::string(tag) + "_dw_" + std::to_string(b);
-      st.push_back({bn,
-                    [=](hipStream_t s) {
-                      DwSplit kk = kb;
-                      kk.slab = slab->p;
-                      TD3_RC(launch_dw_split(ab, kk, s));
-                      if (!local) TD3_HIP(hipEventRecord(first ? ev : ev1, s));
-                      return 0;
-                    },
-                    fb, kname});
-      const int64_t off = n.enc_off >= 0 ? n.enc_off : n.lin[0].offW;
-      const int64_t end = b + 1 < items.size()
-                              ? (items[b + 1].net->enc_off >= 0 ? items[b + 1].net->enc_off : items[b + 1].net->lin[0].offW)
-                              : g.size;
-      TD3_ARG(off >= 0 && end > off && end <= g.size, "internal: bucket range");
-      const int64_t nb = end - off;
-      AdamArgs ar = a.adam;
-      ar.P += off; ar.G += off; ar.M += off; ar.V += off; ar.T += off;
-      W4Map wm;
-      TD3_RC(w4_map(h, g, off, &wm));
-      ar.grad_scale = 1.0f / (float)h->nranks;
-      float* Gb = g.G + off;
-      Stage x{std::string(tag) + "_" + std::to_string(b) + "_allreduce",
-              [=](hipStream_t s) {
-                if (local) {
-                  set_error("a td3_comm_init_local replica steps through td3_train_step_local only");
-                  return -1;
-                }
-                // both buckets on the comm stream (one RCCL stream per communicator),
-                // each behind its own dW; the join waits for the last bucket's Adam
-                TD3_HIP(hipStreamWaitEvent(cs, first ? ev : ev1, 0));
-                ncclResult_t r = ncclAllReduce(Gb, Gb, (size_t)nb, ncclFloat, ncclSum, comm, cs);
-                if (r != ncclSuccess) {
-                  set_error("ncclAllReduce: %s", ncclGetErrorString(r));
-                  return -2;
-                }
-                TD3_RC(launch_adam_flat(ar, nb, pol, cs, &wm));
-                if (!first) TD3_HIP(hipEventRecord(done, cs));
-                return 0;
-              },
-              0, "rccl"};
-      x.collective = which == 1 ? 0 : 1;
-      x.coll_off = off;
-      x.coll_n = nb;
-      x.after = [=](hipStream_t s) { return launch_adam_flat(ar, nb, pol, s, &wm); };
-      exch.push_back(x);
-    }
-    for (auto& x : exch) st.push_back(x);          // dW_0, dW_1, exchange 0 (comm), exchange 1 (step)
-    st.push_back({std::string(tag) + "_join",
-                  [=](hipStream_t s) {
-                    if (local) return 0;            // the seam ran the buckets on its stream
-                    TD3_HIP(hipStreamWaitEvent(s, done, 0));
-                    return 0;
-                  },
-                  0, "(stream join)"});
-    return 0;
-  }
-  if (split) {
+  a.scaled = o.unit_scale ? 1 : 0;
+  w.split = tile64 && Bp % 64 == 0 && TD3_DWSK;
+  *out = w;
+  return 0;
+}
+
+// Network b's problems of `w` as a launch of their own (a bucket of dp.hip's overlapped schedule).
+// They keep the tile_begin of the whole list: only the one-tile-per-workgroup kernels read it, and a
+// bucket is a split-K launch.  Its bytes are not accounted.
+DwWork dw_bucket(const DwWork& w, const std::vector<BwdItem>& items, size_t b) {
+  auto count = [](const NetL& n) { return 4 + (n.lnin ? 1 : 0); };
+  int p0 = 0;
+  for (size_t k = 0; k < b; ++k) p0 += count(*items[k].net);
+  const NetL& n = *items[b].net;
+  DwWork out = w;
+  out.a.nprob = count(n);
+  for (int i = 0; i < out.a.nprob; ++i) out.a.probs[i] = w.a.probs[p0 + i];
+  out.flops = out.bytes = 0;
+  for (int l = 0; l < 4; ++l) out.flops += 2.0 * w.a.Bp * n.lin[l].N * n.lin[l].K;
+  return out;
+}
+
+// One dW launch stage: the split-K pair where the work allows it (B >= 512), else one tile per
+// workgroup.  The one place that spells a dW stage's kernel name.
+int push_dw_stage(const StageCtx& c, std::vector<Stage>& st, const DwWork& w, SlabRef* slab, const std::string& name) {
+  const DwArgs a = w.a;
+  const int blocks = w.blocks;
+  const std::string scaled = a.scaled ? "true" : "false";
+  if (w.split) {
     DwSplit k{};
-    TD3_RC(make_dw_split(h, owned, a, slab, k));
-    st.push_back({std::string(tag) + "_dw",
+    TD3_RC(make_dw_split(c.h, c.owned, a, slab, k));
+    st.push_back({name,
                   [=](hipStream_t s) {
                     DwSplit kk = k;
                     kk.slab = slab->p;
                     return launch_dw_split(a, kk, s);
                   },
-                  flops,
-                  std::string("td3::dwsk_kernel<") + (unit_scale ? "true, " : "false, ") +
-                      (tm == 128 ? "true>" : "false>")});
-    st.back().bytes = dw_bytes;
+                  w.flops, "td3::dwsk_kernel<" + scaled + (k.tm == 128 ? ", true>" : ", false>")});
   } else {
-    st.push_back({std::string(tag) + "_dw", [=](hipStream_t s) { return launch_dw(a, blocks, s); }, flops,
-                  std::string(tile64 ? "td3::dw64_kernel<" : "td3::dw_kernel<") + (unit_scale ? "true>" : "false>")});
-    st.back().bytes = dw_bytes;
+    st.push_back({name, [=](hipStream_t s) { return launch_dw(a, blocks, s); }, w.flops,
+                  (a.tile64 ? "td3::dw64_kernel<" : "td3::dw_kernel<") + scaled + ">"});
   }
-  if (enc_nwg > 0) {
-    EncAdamArgs ea{};
-    for (auto& it : items) {
-      if (it.net->D <= 0) continue;
-      TD3_ARG(ea.nprob < 3, "too many encoders in one dw stage");
-      ea.p[ea.nprob].partial = it.e->partial;
-      ea.p[ea.nprob].off = it.net->enc_off;
-      ea.nprob++;
-    }
-    ea.nwg = enc_nwg;
-    ea.size = EncOff::size(items[0].net->D);
-    ea.adam = a.adam;
-    ea.mode = a.mode;
-    st.push_back({std::string(tag) + "_enc_adam", [=](hipStream_t s) { return launch_enc_adam(ea, s); }, 0,
-                  "td3::enc_adam_kernel"});
+  st.back().bytes = w.bytes;
+  return 0;
+}
+
+// TD3_particles: the encoder partial slabs of `items`, reduced and stepped in one launch
+static int push_enc_adam_stage(std::vector<Stage>& st, const std::vector<BwdItem>& items, const DwWork& w,
+                               int enc_nwg, const char* tag) {
+  EncAdamArgs ea{};
+  for (auto& it : items) {
+    if (it.net->D <= 0) continue;
+    TD3_ARG(ea.nprob < 3, "too many encoders in one dw stage");
+    ea.p[ea.nprob].partial = it.e->partial;
+    ea.p[ea.nprob].off = it.net->enc_off;
+    ea.nprob++;
   }
-  AdamArgs aa = a.adam;
-  if (dp) aa.grad_scale = 1.0f / (float)h->nranks;
-  const int pol = polyak ? 1 : 0;
-  if (dp && !wn && dp_shard(h)) {
-    // Sharded optimizer step (ZeRO-1 form): the summed gradient reaches only this
-    // rank's slice (ncclReduceScatter, in place), Adam runs on that slice alone (the moments of the
-    // other slices live on their owners), ncclAllGather brings every rank the updated parameters,
-    // then Polyak runs replicated over the whole arena (the same inputs on every rank: the replicas
-    // stay bit-identical, each element computed once).  Same bytes on the links as the all-reduce,
-    // one extra collective launch, 1/N of the Adam pass.
-    const int N = h->nranks, R = h->rank;
-    const int64_t slice = shard_slice(g, N);
-    TD3_ARG(N * slice <= g.cap, "internal: shard slices past the arena");
-    h->dp_sharded = true;
-    ncclComm_t comm = h->comm;
-    float* G = g.G;
-    float* Pp = g.P;
-    const bool local = h->local != nullptr;
-    AdamArgs as = aa;
-    as.P += R * slice; as.G += R * slice; as.M += R * slice; as.V += R * slice; as.T += R * slice;
-    Stage x{std::string(tag) + "_rs_adam_ag",
-            [=](hipStream_t s) {
-              if (local) {
-                set_error("a td3_comm_init_local replica steps through td3_train_step_local only");
-                return -1;
-              }
-              ncclResult_t r = ncclReduceScatter(G, G + R * slice, (size_t)slice, ncclFloat, ncclSum, comm, s);
-              if (r != ncclSuccess) {
-                set_error("ncclReduceScatter: %s", ncclGetErrorString(r));
-                return -2;
-              }
-              TD3_RC(launch_adam_flat(as, slice, 0, s));
-              r = ncclAllGather(Pp + R * slice, Pp, (size_t)slice, ncclFloat, comm, s);
-              if (r != ncclSuccess) {
-                set_error("ncclAllGather: %s", ncclGetErrorString(r));
-                return -2;
-              }
-              return 0;
-            },
-            0, "rccl"};
-    x.collective = which == 1 ? 0 : 1;
-    x.coll_slice = slice;
-    x.after = [=](hipStream_t s) { return launch_adam_flat(as, slice, 0, s); };
-    st.push_back(x);
-    if (polyak && h->w4_build) {        // Polyak and both images in one pass over the gathered arena
-      float* Tp = g.T;
-      const int64_t n = g.size;
-      const float tau = (float)h->cfg.tau;
-      W4Map wm;
-      TD3_RC(w4_map(h, g, 0, &wm));
-      st.push_back({std::string(tag) + "_polyak", [=](hipStream_t s) { return launch_polyak_w4(Tp, Pp, n, tau, wm, s); },
-                    0, "td3::polyak_w4_kernel"});
-      return 0;
-    }
-    if (polyak) {
-      float* Tp = g.T;
-      const int64_t n = g.size;
-      const float tau = (float)h->cfg.tau;
-      st.push_back({std::string(tag) + "_polyak", [=](hipStream_t s) { return launch_polyak_flat(Tp, Pp, n, tau, s); },
-                    0, "td3::polyak_flat_kernel"});
-    }
-    TD3_RC(push_w4_pack(h, st, g, false, tag));
-    return 0;
-  }
-  if (dp) {
-    ncclComm_t comm = h->comm;
-    float* G = g.G;
-    const int64_t n = g.size;
-    const bool local = h->local != nullptr;
-    st.push_back({std::string(tag) + "_allreduce",
-                  [=](hipStream_t s) {
-                    if (local) {
-                      set_error("a td3_comm_init_local replica steps through td3_train_step_local only");
-                      return -1;
-                    }
-                    ncclResult_t r = ncclAllReduce(G, G, (size_t)n, ncclFloat, ncclSum, comm, s);
-                    if (r != ncclSuccess) {
-                      set_error("ncclAllReduce: %s", ncclGetErrorString(r));
-                      return -2;
-                    }
-                    return 0;
-                  },
-                  0, "rccl"});
-    st.back().collective = which == 1 ? 0 : 1;     // AdamArgs::which 1 = actor -> group 0
-  }
-  if (wn) {
-    WnArgs w = g.wn;
-    w.adam = aa;
-    w.mode = kWnAdam;
-    w.polyak = pol;
-    st.push_back({std::string(tag) + "_wn", [=](hipStream_t s) { return launch_wn(w, s); }, 0, "td3::wn_kernel"});
-  } else if (dp) {
-    const int64_t n = g.size;
-    W4Map wm;
-    TD3_RC(w4_map(h, g, 0, &wm));
-    st.push_back({std::string(tag) + "_adam",
-                  [=](hipStream_t s) { return launch_adam_flat(aa, n, pol, s, &wm); }, 0,
-                  "td3::adam_flat_kernel"});
-  }
+  ea.nwg = enc_nwg;
+  ea.size = EncOff::size(items[0].net->D);
+  ea.adam = w.a.adam;
+  ea.mode = w.a.mode;
+  st.push_back({std::string(tag) + "_enc_adam", [=](hipStream_t s) { return launch_enc_adam(ea, s); }, 0,
+                "td3::enc_adam_kernel"});
+  return 0;
+}
+
+// Weight normalization's optimizer step: the dW stage's gradient -> (dg, dv), Adam (+ Polyak)
+int push_wn_stage(std::vector<Stage>& st, const Group& g, const AdamArgs& adam, bool polyak, const char* tag) {
+  WnArgs w = g.wn;
+  w.adam = adam;
+  w.mode = kWnAdam;
+  w.polyak = polyak ? 1 : 0;
+  st.push_back({std::string(tag) + "_wn", [=](hipStream_t s) { return launch_wn(w, s); }, 0, "td3::wn_kernel"});
+  return 0;
+}
+
+// Weight / bias / LN grads of every layer of `items` (o.enc_nwg, TD3_particles: then the encoders'),
+// then the optimizer step: fused into the dW launch on one GPU; wn_kernel under weight normalization;
+// in a data-parallel plan the dW kernels write the gradient only and dp.hip's schedule follows.
+int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
+                 const char* tag, const DwOpts& o) {
+  DwWork w;
+  TD3_RC(make_dw_work(c, g, items, o, &w));
+  const bool dp = c.h->comm != nullptr || c.h->local != nullptr;
+  if (dp && dp_buckets(c.h, g, items, o, w)) return add_dp_overlapped(c, st, g, items, tag, o, w);
+  TD3_RC(push_dw_stage(c, st, w, o.slab, std::string(tag) + "_dw"));
+  if (o.enc_nwg > 0) TD3_RC(push_enc_adam_stage(st, items, w, o.enc_nwg, tag));
+  if (dp) return add_dp_optimizer(c.h, st, g, w.a.adam, o.polyak, tag);
+  if (g.wn.nlin > 0) return push_wn_stage(st, g, w.a.adam, o.polyak, tag);
   return 0;
 }
 

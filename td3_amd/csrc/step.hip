@@ -862,7 +862,7 @@ static int run_body(td3_handle* h, int actor_phase, int inj, hipStream_t s, Ring
 int build_plan(td3_handle* h, int B) {
   const bool was_sharded = h->dp_sharded && h->nranks > 1;
   h->bc_step = 0;                             // the last BC step's lambda / row errors go with the plan
-  h->dp_sharded = false;                      // set again by add_dw_stage when it shards
+  h->dp_sharded = false;                      // set again by dp.hip add_dp_sharded
   // the profiled stage list lives in the plan being replaced
   h->last_body = nullptr;
   h->last_ring = nullptr;
