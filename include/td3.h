@@ -795,6 +795,17 @@ int td3_debug_log_launch(td3_handle* h, void* stream);
  * must then fail (rc < 0, the kernel publishes its flag with the failure bit) and the next query must
  * be correct again (the host re-zeroes the hand-off counters). */
 int td3_debug_act_fail(td3_handle* h, int n);
+/* Test instrumentation: which route a featured query of n rows takes (eval_q != 0: td3_eval_q, else
+ * td3_select_action; device != 0: their _device forms), written into buf (len bytes, NUL-terminated) as a
+ * comma-separated list.  The first token says where the query's rows travel: "args" (in the kernel
+ * arguments), "mapped" (mapped host memory) or "device" (device scratch); the rest are the HIP kernels the
+ * query would launch, in order, named as td3_stage_kernel names them, e.g.
+ * "args,td3::act_kernel<4, 16>" or "args,td3::gemv01_kernel<2>,td3::gemv_kernel<2>,td3::head_kernel".
+ * A query that runs a plan's stage list gives the stages' kernels (the device forms' row packing in front
+ * of the list and their exploration epilogue behind it are not named).  Builds the query plan of pad32(n)
+ * rows if it does not exist yet; launches nothing.  The answer comes from the function the queries
+ * themselves dispatch on. */
+int td3_debug_query_route(td3_handle* h, int n, int eval_q, int device, char* buf, int len);
 /* Test seam of the wide heads (action width > 8): the dynamic LDS bytes of the calling thread's last row-kernel
  * launch, i.e. of the weight rows its workgroups staged (0: every head was requested block by block, e.g.
  * under TD3_WIDE_HEADS=0; -1: no row launch yet).  Launches replayed from a captured graph do not count: use it

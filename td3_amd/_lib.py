@@ -213,6 +213,7 @@ SIGNATURES = {
     "td3_debug_log_launch": (C.c_int, [_P, _P]),
     "td3_debug_row_lds": (C.c_int, []),
     "td3_debug_act_fail": (C.c_int, [_P, C.c_int]),
+    "td3_debug_query_route": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "td3_last_error": (C.c_char_p, []),
 }
 

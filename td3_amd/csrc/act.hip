@@ -51,6 +51,7 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
   }
   std::unique_ptr<ActPlan> A(new ActPlan());
   A->Bp = Bp;
+  A->dev = dev;
   const bool norm = h->cfg.norm == 1;
   const NetL& an = h->actor.nets[0];
   const NetL& q1 = h->critic.nets[0];
@@ -141,7 +142,7 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
     a.Bp = Bp;
     a.max_action = h->cfg.max_action;
     A->head_act = a;
-    A->act.push_back({"act_head", [=](hipStream_t s) { return launch_heads(a, 1, s); }, 0});
+    A->act.push_back({"act_head", [=](hipStream_t s) { return launch_heads(a, 1, s); }, 0, "td3::head_kernel"});
   }
   {
     std::vector<FwdItem> f = {{&q1, h->critic.P, &A->Q[0], false, false},
@@ -162,7 +163,7 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
     a.Bp = Bp;
     a.max_action = h->cfg.max_action;
     A->head_q = a;
-    A->evalq.push_back({"evq_head", [=](hipStream_t s) { return launch_heads(a, 2, s); }, 0});
+    A->evalq.push_back({"evq_head", [=](hipStream_t s) { return launch_heads(a, 2, s); }, 0, "td3::head_kernel"});
   }
   if (A->act1) {
     auto mk = [&](ActArgs& a, const Gemv01Args& g, const GemvArgs& l2, std::initializer_list<const NetL*> nets,
@@ -195,6 +196,19 @@ static int build_act(td3_handle* h, int Bp, ActPlan** out, bool dev = false) {
   return 0;
 }
 
+// The one place that decides how a featured query of n rows runs on plan A (q: eval_q, else
+// select_action).  Up to kGemvRows rows of a host query skip the 32-row stage list: one act_kernel launch
+// (ActPlan::act1), else the launch chain, whose first two layers are one gemv01 launch when both
+// networks' layer 0 is narrow (ActPlan::gemv01).  act_kernel and gemv01_kernel take the rows in their
+// arguments; everything else reads them from the plan's inputs, mapped host memory or device scratch.
+QueryRoute query_route(ActPlan* A, int n, bool q) {
+  QueryRoute r{kQueryStages, A->hio ? kRowsMapped : kRowsDevice, q ? &A->evalq : &A->act};
+  if (A->dev || !A->gemv || n > kGemvRows) return r;
+  r.kind = A->act1 ? kQueryAct1 : A->gemv01 ? kQueryGemv01 : kQueryGemv;
+  if (r.kind != kQueryGemv) r.rows = kRowsArgs;
+  return r;
+}
+
 // select_action / eval_q of TD3_particles (TD3_particles.py:153-164): the particles of the n
 // query states are uploaded packed ([n][N*D], rows 0..n-1), the encoders read them in place.
 // dev: a plan of the device-resident queries (td3_handle::act_dev, as build_act's): device scratch at
@@ -210,6 +224,7 @@ static int build_act_particles(td3_handle* h, int Bp, ActPlan** out, bool dev = 
   }
   std::unique_ptr<ActPlan> A(new ActPlan());
   A->Bp = Bp;
+  A->dev = dev;
   const bool norm = h->cfg.norm == 1;
   const bool cdq = h->cdq != 0;
   const int N = h->N, D = h->D, ad = h->ad;
@@ -379,14 +394,14 @@ static int wait_flags(volatile unsigned* f, int nprob, unsigned seq, hipStream_t
   return 0;
 }
 
-// A featured query of n <= kGemvRows rows: layers 0 and 1 in one gemv01 launch when layer 0 is
-// narrow (the query rows [x0 | x1] in its arguments), else one gemv launch per layer; then the
-// head over 4 rows.
-static int run_gemv(const ActPlan* A, bool q, int n, const float* x0, int c0, const float* x1, int c1,
-                    hipStream_t s) {
+// A featured query of n <= kGemvRows rows on the route query_route chose (kind: not kQueryStages): one
+// act_kernel launch; or layers 0 and 1 in one gemv01 launch when layer 0 is narrow (the query rows
+// [x0 | x1] in its arguments), else one gemv launch per layer, then the head over 4 rows.
+static int run_gemv(const ActPlan* A, QueryKind kind, bool q, int n, const float* x0, int c0, const float* x1,
+                    int c1, hipStream_t s) {
   const GemvArgs(&gv)[3] = q ? A->gv_q : A->gv_act;
   const int nprob = q ? 2 : 1;
-  if (A->act1) {                                        // the whole query in one launch
+  if (kind == kQueryAct1) {                             // the whole query in one launch
     ActArgs a = q ? A->a1_q : A->a1_act;
     a.g.l1.B = n;
     const int K0 = c0 + c1;
@@ -407,7 +422,7 @@ static int run_gemv(const ActPlan* A, bool q, int n, const float* x0, int c0, co
     return wait_flags(M->hflag[q ? 1 : 0], nprob, a.seq, s, a.ctr);
   }
   int l = 0;
-  if (A->gemv01) {
+  if (kind == kQueryGemv01) {
     Gemv01Args g = q ? A->g01_q : A->g01_act;
     g.l1.B = n;
     const int K0 = c0 + c1;
@@ -456,20 +471,17 @@ int td3_select_action(td3_handle* h, const float* state, float* action_out, int 
   TD3_RC(build_act(h, pad32(n), &A));
   hipStream_t s;
   TD3_RC(query_stream(h, &s));
-  if (A->act1 && A->gemv && n <= kGemvRows) {
+  const QueryRoute r = query_route(A, n, false);
+  if (r.kind == kQueryAct1) {
     // the query travels in the kernel arguments and the outputs of the previous query were read
     // before it returned: no stream synchronize on either side (wait_flags)
-    TD3_RC(run_gemv(A, false, n, state, h->sd, nullptr, 0, s));
+    TD3_RC(run_gemv(A, r.kind, false, n, state, h->sd, nullptr, 0, s));
     return query_done(h, s, get_rows(action_out, h->ad, A->out, A->hout, A->ldo, n, s));
   }
   if (A->hio) TD3_HIP(hipStreamSynchronize(s));
-  if (A->gemv && n <= kGemvRows) {
-    if (!A->gemv01) TD3_RC(put_rows(A, A->X_S, A->hX_S, pad32(h->sd), 0, state, n, h->sd, s));
-    TD3_RC(run_gemv(A, false, n, state, h->sd, nullptr, 0, s));
-  } else {
-    TD3_RC(put_rows(A, A->X_S, A->hX_S, pad32(h->sd), 0, state, n, h->sd, s));
-    TD3_RC(run_stages(A->act, s));
-  }
+  if (r.rows != kRowsArgs) TD3_RC(put_rows(A, A->X_S, A->hX_S, pad32(h->sd), 0, state, n, h->sd, s));
+  if (r.kind == kQueryStages) TD3_RC(run_stages(*r.stages, s));
+  else TD3_RC(run_gemv(A, r.kind, false, n, state, h->sd, nullptr, 0, s));
   if (A->hio) TD3_HIP(hipStreamSynchronize(s));
   return query_done(h, s, get_rows(action_out, h->ad, A->out, A->hout, A->ldo, n, s));
 }
@@ -483,19 +495,19 @@ int td3_eval_q(td3_handle* h, const float* state, const float* action, float* q_
   TD3_RC(build_act(h, pad32(n), &A));
   hipStream_t s = h->stream;
   const int ld = pad32(h->sd + h->ad);
-  const bool small = A->gemv && n <= kGemvRows;
-  if (A->act1 && small) {        // one launch, completion flags polled on the host (no stream syncs)
-    TD3_RC(run_gemv(A, true, n, state, h->sd, action, h->ad, s));
+  const QueryRoute r = query_route(A, n, true);
+  if (r.kind == kQueryAct1) {    // one launch, completion flags polled on the host (no stream syncs)
+    TD3_RC(run_gemv(A, r.kind, true, n, state, h->sd, action, h->ad, s));
     TD3_RC(get_rows(q_out, 1, A->q[0], A->hq[0], 1, n, s));
     return get_rows(q_out + n, 1, A->q[1], A->hq[1], 1, n, s);
   }
   if (A->hio) TD3_HIP(hipStreamSynchronize(s));
-  if (!small || !A->gemv01) {
+  if (r.rows != kRowsArgs) {
     TD3_RC(put_rows(A, A->X_SA, A->hX_SA, ld, 0, state, n, h->sd, s));
     TD3_RC(put_rows(A, A->X_SA, A->hX_SA, ld, h->sd, action, n, h->ad, s));
   }
-  if (small) TD3_RC(run_gemv(A, true, n, state, h->sd, action, h->ad, s));
-  else TD3_RC(run_stages(A->evalq, s));
+  if (r.kind == kQueryStages) TD3_RC(run_stages(*r.stages, s));
+  else TD3_RC(run_gemv(A, r.kind, true, n, state, h->sd, action, h->ad, s));
   if (A->hio) TD3_HIP(hipStreamSynchronize(s));
   TD3_RC(get_rows(q_out, 1, A->q[0], A->hq[0], 1, n, s));
   return get_rows(q_out + n, 1, A->q[1], A->hq[1], 1, n, s);
@@ -556,7 +568,7 @@ int td3_select_action_device(td3_handle* h, const float* state, int n, const td3
   hipStream_t s;
   TD3_RC(device_query_stream(h, stream, &s));
   TD3_RC(launch_pack(state, h->sd, n, Bp, {{A->X_S, pad32(h->sd), 0}}, s));
-  TD3_RC(run_stages(A->act, s));
+  TD3_RC(run_stages(*query_route(A, n, false).stages, s));
   return explore_rows(h, A, n, ex, action_out, s);
 }
 
@@ -572,9 +584,42 @@ int td3_eval_q_device(td3_handle* h, const float* state, const float* action, in
   TD3_RC(device_query_stream(h, stream, &s));
   TD3_RC(launch_pack(state, h->sd, n, Bp, {{A->X_SA, ld, 0}}, s));
   TD3_RC(launch_pack(action, h->ad, n, Bp, {{A->X_SA, ld, h->sd}}, s));
-  TD3_RC(run_stages(A->evalq, s));
+  TD3_RC(run_stages(*query_route(A, n, true).stages, s));
   for (int j = 0; j < 2; ++j)        // the live rows of Q_j -> q_out[j][0..n)
     TD3_RC(launch_pack(A->q[j], 1, n, n, {{q_out + (size_t)j * n, 1, 0}}, s));
+  return 0;
+}
+
+int td3_debug_query_route(td3_handle* h, int n, int eval_q, int device, char* buf, int len) {
+  TD3_ARG(h && buf && len > 0, "null argument");
+  TD3_ARG(!h->particles, "featured learners only");
+  TD3_ARG(n > 0, "n must be positive");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  ActPlan* A;
+  TD3_RC(build_act(h, pad32(n), &A, device != 0));
+  const bool q = eval_q != 0;
+  const QueryRoute r = query_route(A, n, q);
+  const int R = gemv_rows(n);
+  std::string out = r.rows == kRowsArgs ? "args" : r.rows == kRowsMapped ? "mapped" : "device";
+  char name[64];
+  if (r.kind == kQueryAct1) {
+    snprintf(name, sizeof(name), ",td3::act_kernel<%d, %d>", R, act_kq((q ? A->a1_q : A->a1_act).g.K0));
+    out += name;
+  } else if (r.kind == kQueryStages) {
+    for (const Stage& st : *r.stages) out += "," + st.kernel;
+  } else {
+    int l = 0;
+    if (r.kind == kQueryGemv01) {
+      snprintf(name, sizeof(name), ",td3::gemv01_kernel<%d>", R);
+      out += name;
+      l = 2;
+    }
+    snprintf(name, sizeof(name), ",td3::gemv_kernel<%d>", R);
+    for (; l < 3; ++l) out += name;
+    out += ",td3::head_kernel";
+  }
+  TD3_ARG((int)out.size() < len, "buffer too small");
+  memcpy(buf, out.c_str(), out.size() + 1);
   return 0;
 }
 

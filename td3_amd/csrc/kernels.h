@@ -480,6 +480,9 @@ struct HeadArgs {
 // select_action / eval_q of up to kGemvRows query rows: each hidden Linear as wave dot products
 // (a 32-row MFMA tile would compute 31 pad rows, each workgroup walking K serially).
 constexpr int kGemvRows = 4;
+// The rows a wave of gemv_kernel / gemv01_kernel / act_kernel holds for a query of B live rows: the
+// template argument R their launchers dispatch on (3 rows run R = 4 with one dead row).
+constexpr int gemv_rows(int B) { return B <= 1 ? 1 : B == 2 ? 2 : 4; }
 struct GemvProb {
   const float* X; int ldx; int K;       // input rows: the query, or the previous layer's ReLU output
   const float* lng; const float* lnb;   // LayerNorm of the input (nullable: layer 0 / norm=None)
@@ -521,6 +524,8 @@ struct ActArgs {
 };
 constexpr unsigned kActFailed = 0x80000000u;   // flag bit: the query's outputs are not valid
 constexpr int kActFailInc = 1 << 16;           // a timed-out workgroup's arrival on the layer-2 counter
+// act_kernel's template argument KQ (float4 steps of a layer-0 row) for a layer 0 of K0 inputs
+constexpr int act_kq(int K0) { return K0 <= 32 ? 8 : 16; }
 int launch_act(const ActArgs& a, int nprob, hipStream_t s);
 
 // dZ = relu'(LN_bwd(dU)) on full rows (layer 0, where no GEMM follows).

@@ -318,8 +318,9 @@ int launch_gemv(const GemvArgs& a, int nprob, hipStream_t s) {
       return -1;
     }
   const dim3 grid((N + 15) / 16, nprob);
-  if (a.B == 1) hipLaunchKernelGGL(gemv_kernel<1>, grid, dim3(256), 0, s, a);
-  else if (a.B == 2) hipLaunchKernelGGL(gemv_kernel<2>, grid, dim3(256), 0, s, a);
+  const int R = gemv_rows(a.B);
+  if (R == 1) hipLaunchKernelGGL(gemv_kernel<1>, grid, dim3(256), 0, s, a);
+  else if (R == 2) hipLaunchKernelGGL(gemv_kernel<2>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(gemv_kernel<4>, grid, dim3(256), 0, s, a);
   TD3_HIP(hipGetLastError());
   return 0;
@@ -347,17 +348,18 @@ int launch_act(const ActArgs& a, int nprob, hipStream_t s) {
       return -1;
     }
   const dim3 grid((N1 + 15) / 16, nprob);
-  if (a.g.ldw0 < (a.g.K0 <= 32 ? 32 : 64)) {
+  const int R = gemv_rows(B), KQ = act_kq(a.g.K0);
+  if (a.g.ldw0 < 4 * KQ) {
     set_error("launch_act: layer-0 rows of %d floats (K0 %d)", a.g.ldw0, a.g.K0);
     return -1;
   }
-  if (a.g.K0 <= 32) {
-    if (B == 1) hipLaunchKernelGGL((act_kernel<1, 8>), grid, dim3(256), 0, s, a);
-    else if (B == 2) hipLaunchKernelGGL((act_kernel<2, 8>), grid, dim3(256), 0, s, a);
+  if (KQ == 8) {
+    if (R == 1) hipLaunchKernelGGL((act_kernel<1, 8>), grid, dim3(256), 0, s, a);
+    else if (R == 2) hipLaunchKernelGGL((act_kernel<2, 8>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((act_kernel<4, 8>), grid, dim3(256), 0, s, a);
   } else {
-    if (B == 1) hipLaunchKernelGGL((act_kernel<1, 16>), grid, dim3(256), 0, s, a);
-    else if (B == 2) hipLaunchKernelGGL((act_kernel<2, 16>), grid, dim3(256), 0, s, a);
+    if (R == 1) hipLaunchKernelGGL((act_kernel<1, 16>), grid, dim3(256), 0, s, a);
+    else if (R == 2) hipLaunchKernelGGL((act_kernel<2, 16>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((act_kernel<4, 16>), grid, dim3(256), 0, s, a);
   }
   TD3_HIP(hipGetLastError());
@@ -379,8 +381,9 @@ int launch_gemv01(const Gemv01Args& a, int nprob, hipStream_t s) {
       return -1;
     }
   const dim3 grid((N + 15) / 16, nprob);
-  if (a.l1.B == 1) hipLaunchKernelGGL(gemv01_kernel<1>, grid, dim3(256), 0, s, a);
-  else if (a.l1.B == 2) hipLaunchKernelGGL(gemv01_kernel<2>, grid, dim3(256), 0, s, a);
+  const int R = gemv_rows(a.l1.B);
+  if (R == 1) hipLaunchKernelGGL(gemv01_kernel<1>, grid, dim3(256), 0, s, a);
+  else if (R == 2) hipLaunchKernelGGL(gemv01_kernel<2>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(gemv01_kernel<4>, grid, dim3(256), 0, s, a);
   TD3_HIP(hipGetLastError());
   return 0;

@@ -212,6 +212,7 @@ struct ActPlan {       // select_action / eval_q at small batch
   int Bp = 0;
   float* scratch = nullptr;
   float* hio = nullptr;  // mapped pinned block (Bp <= kMappedRows), else nullptr
+  bool dev = false;      // a plan of the device-resident queries (td3_handle::act_dev)
   // device addresses the stages use; the h* twins are their host views when mapped
   float *X_S = nullptr, *X_SA = nullptr, *out = nullptr, *q[2] = {nullptr, nullptr};
   float *XQ2 = nullptr, *pbatch = nullptr;   // particles
@@ -239,6 +240,22 @@ struct ActPlan {       // select_action / eval_q at small batch
   std::vector<void*> tables;
   std::vector<Stage> act, evalq;
 };
+
+// How a featured query of n rows runs on plan A (act.hip: td3_select_action, td3_eval_q, run_gemv and
+// td3_debug_query_route all ask query_route): the launches, and where the query's rows travel.
+enum QueryKind {
+  kQueryAct1,     // one act_kernel launch, completion flags polled on the host
+  kQueryGemv01,   // gemv01_kernel (layers 0 + 1) -> gemv_kernel (layer 2) -> head_kernel
+  kQueryGemv,     // gemv_kernel per hidden layer -> head_kernel
+  kQueryStages,   // the plan's stage list (A->act / A->evalq)
+};
+enum QueryRows { kRowsArgs, kRowsMapped, kRowsDevice };   // kernel arguments / mapped host block / device scratch
+struct QueryRoute {
+  QueryKind kind;
+  QueryRows rows;
+  std::vector<Stage>* stages;   // kQueryStages: the list to run (q: evalq, else act)
+};
+QueryRoute query_route(ActPlan* A, int n, bool q);
 
 // Carves an ActPlan's query inputs / outputs from the mapped block, or from the device scratch.
 struct IoCarve {

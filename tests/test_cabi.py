@@ -33,6 +33,19 @@ def test_header_symbols_exported(lib):
         assert s in _lib.SIGNATURES, f"{s} not bound in td3_amd/_lib.py"
 
 
+def test_query_route_export(lib):
+    """td3_debug_query_route is declared, exported and bound with its six arguments, and refuses a
+    null handle without writing into the caller's buffer."""
+    from td3_amd import _lib
+    assert "td3_debug_query_route" in _header_symbols()
+    res, args = _lib.SIGNATURES["td3_debug_query_route"]
+    assert res is C.c_int and len(args) == 6
+    buf = C.create_string_buffer(b"\xab" * 63, 64)
+    assert lib.td3_debug_query_route(None, 1, 0, 0, buf, 64) == -1
+    assert b"null argument" in lib.td3_last_error()
+    assert buf.raw[:63] == b"\xab" * 63
+
+
 def test_no_cpu_fallback_symbols(lib):
     # the product library must not reference the oracle
     data = open(os.path.join(ROOT, "td3_amd", "libtd3hip.so"), "rb").read()
