@@ -750,6 +750,11 @@ int td3_profile_stages(td3_handle* h, rb_handle* rb, int batch, int actor_phase,
 const char* td3_stage_name(td3_handle* h, int i);
 /* HIP kernel function launched by stage i (the name rocprofv3 reports). */
 const char* td3_stage_kernel(td3_handle* h, int i);
+/* Debug: stage i of the stage list the handle's last step ran (td3_train_step_local records it, as
+ * td3_profile_stages does; a rebuilt plan forgets it): its name, or with `kernel` != 0 its HIP kernel.
+ * "" out of range -- the list ends there.  A td3_comm_init_local replica cannot run
+ * td3_profile_stages (its collective stages refuse to launch); this reads what its step left. */
+const char* td3_debug_last_stage(td3_handle* h, int i, int kernel);
 /* Re-launch one stage `iters` times back-to-back (captured in one hipGraph, replayed between
  * two HIP events on the handle stream, after one full step at `batch`); returns mean ms per
  * launch.  Stage 0 is the stand-alone replay-ring gather (gather_kernel) of the profiled ring. */

@@ -203,6 +203,7 @@ SIGNATURES = {
     "td3_profile_stages": (C.c_int, [_P, _P, C.c_int, C.c_int, _F, C.c_int, C.POINTER(C.c_int)]),
     "td3_stage_name": (C.c_char_p, [_P, C.c_int]),
     "td3_stage_kernel": (C.c_char_p, [_P, C.c_int]),
+    "td3_debug_last_stage": (C.c_char_p, [_P, C.c_int, C.c_int]),
     "td3_time_stage": (C.c_int, [_P, C.c_int, C.c_int, _F]),
     "td3_probe_kernel": (C.c_int, [_P, _P, C.c_int, C.c_char_p, C.c_int, _F, C.POINTER(C.c_int)]),
     "td3_stage_flops": (C.c_double, [_P, C.c_int]),

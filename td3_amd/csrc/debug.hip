@@ -66,6 +66,12 @@ const char* td3_stage_kernel(td3_handle* h, int i) {
   return h->stage_kernels[i].c_str();
 }
 
+const char* td3_debug_last_stage(td3_handle* h, int i, int kernel) {
+  if (!h || !h->last_body || i < 0 || i >= (int)h->last_body->size()) return "";
+  const Stage& st = (*h->last_body)[i];
+  return kernel ? st.kernel.c_str() : st.name.c_str();
+}
+
 double td3_stage_flops(td3_handle* h, int i) {
   if (!h || !h->last_body || i <= 0 || i > (int)h->last_body->size()) return 0.0;
   return (*h->last_body)[i - 1].flops;

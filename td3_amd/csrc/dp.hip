@@ -281,6 +281,18 @@ int consolidate_moments(td3_handle* h, int which) {
   return 0;
 }
 
+// Whether two learners have the same networks, tensor by tensor: every dimension that sizes one.  The arena
+// sizes alone do not say so: widths pad to 32, and (state, action) = (17, 6) and (3, 1) fill the same floats.
+static bool same_shape(const td3_config& a, const td3_config& b) {
+  if (a.particles != b.particles || a.norm != b.norm || a.state_dim != b.state_dim || a.action_dim != b.action_dim)
+    return false;
+  if (a.particles && (a.n_particles != b.n_particles || a.particle_dim != b.particle_dim || !a.cdq != !b.cdq))
+    return false;
+  for (int i = 0; i < 3; ++i)
+    if (a.actor_hidden[i] != b.actor_hidden[i] || a.critic_hidden[i] != b.critic_hidden[i]) return false;
+  return true;
+}
+
 }  // namespace td3
 
 using namespace td3;
@@ -340,9 +352,7 @@ int td3_comm_init_local(td3_handle** hs, int n) {
     TD3_ARG(!hs[k]->log, "the training log is enabled on a handle (data-parallel logging is not supported)");
     TD3_ARG(hs[k]->bc_alpha == 0.0, "TD3+BC is on for a handle (td3_set_bc): data-parallel BC is not supported");
     TD3_ARG(hs[k]->cfg.device == hs[0]->cfg.device, "local replicas share one device");
-    TD3_ARG(hs[k]->particles == hs[0]->particles && hs[k]->actor.size == hs[0]->actor.size &&
-                hs[k]->critic.size == hs[0]->critic.size && hs[k]->cfg.norm == hs[0]->cfg.norm,
-            "local replicas must have the same configuration");
+    TD3_ARG(same_shape(hs[k]->cfg, hs[0]->cfg), "local replicas must have the same configuration");
     for (int j = 0; j < k; ++j) TD3_ARG(hs[j] != hs[k], "a handle appears twice");
   }
   auto g = std::make_shared<LocalGroup>();

@@ -51,7 +51,8 @@ def train_local(policies, buffers, batch_size, indices=None, noise=None, stats=F
     """One ``TD3.train(buffer_k, batch_size)`` of every replica k of a ``local_group``.
 
     ``indices`` [n, B] / ``noise`` [n, B, ad] replace the Philox draws (parity tests); with
-    ``stats`` a list of per-replica dicts (critic loss, actor loss, y, q1, q2) is returned."""
+    ``stats`` a list of per-replica dicts (critic loss, actor loss, y, q1, q2, the drawn rows idx)
+    is returned."""
     n = len(policies)
     lib = policies[0]._lib
     B = int(batch_size)
@@ -71,9 +72,9 @@ def train_local(policies, buffers, batch_size, indices=None, noise=None, stats=F
         st = (_lib.td3_step_stats * n)()
         nq = ad if hasattr(policies[0], "n_particles") else 1     # particle Q heads: one per action
         for k in range(n):
-            arrs = [np.empty((B, nq), np.float32) for _ in range(3)]
+            arrs = [np.empty((B, nq), np.float32) for _ in range(3)] + [np.empty(B, np.int64)]
             keep.append(arrs)
-            st[k].y, st[k].q1, st[k].q2 = (a.ctypes.data for a in arrs)
+            st[k].y, st[k].q1, st[k].q2, st[k].idx = (a.ctypes.data for a in arrs)
     check(lib.td3_train_step_local(hs, rbs, n, B, _lib.i64ptr(ix) if ix is not None else None,
                                    _lib.fptr(nz) if nz is not None else None, st), "td3_train_step_local")
     if not stats:
@@ -81,7 +82,7 @@ def train_local(policies, buffers, batch_size, indices=None, noise=None, stats=F
     out = []
     for k in range(n):
         d = {"critic_loss": st[k].critic_loss, "actor_step": bool(st[k].actor_step),
-             "y": keep[k][0], "q1": keep[k][1], "q2": keep[k][2]}
+             "y": keep[k][0], "q1": keep[k][1], "q2": keep[k][2], "idx": keep[k][3]}
         if st[k].actor_step:
             d["actor_loss"] = st[k].actor_loss
         out.append(d)

@@ -134,13 +134,27 @@ def stage_kernels(pol, rb, B, actor_phase):
             for i in range(n.value)]
 
 
-def oracle_dp_step(L, batch, noise, n, step_fn=None):
+def dp_mean(grads, n):
+    """The replicas' gradient dicts reduced as the product reduces them: summed in replica order
+    (((g0 + g1) + g2) ..., as local_sum_kernel) and scaled by float32(1/n) (adam_flat_kernel's
+    grad_scale)."""
+    red = {}
+    for name, g0 in grads[0].items():
+        acc = np.asarray(g0, np.float32)
+        for j in range(1, len(grads)):
+            acc = (acc + np.asarray(grads[j][name], np.float32)).astype(np.float32)
+        red[name] = (acc * np.float32(1.0 / n)).astype(np.float32)
+    return red
+
+
+def oracle_dp_step(L, batch, noise, n, step_fn=None, reduce=dp_mean):
     """The oracle's restatement of the product's data-parallel step: n Learner copies
     in lock-step (threads), replica k on rows [k*b, (k+1)*b) of the batch; each phase's gradients
     summed over replicas in replica order (((g0 + g1) + g2) ..., as local_sum_kernel) and scaled by
     float32(1/n) (adam_flat_kernel's grad_scale) before the oracle's own Adam + Polyak.  Returns
     replica 0's Learner (all replicas end identical).  Against this, the GPU data-parallel step
-    differs only by the summation order inside each shard, as the single-device tests do."""
+    differs only by the summation order inside each shard, as the single-device tests do.
+    ``reduce`` (tests of the tests: a deliberately wrong reduction) replaces ``dp_mean``."""
     import copy
     import threading
     step_fn = step_fn or orc.featured_train_step
@@ -158,11 +172,7 @@ def oracle_dp_step(L, batch, noise, n, step_fn=None):
             bar.wait()
             if k == 0:
                 red.clear()
-                for name, g0 in slots[0].items():
-                    acc = np.asarray(g0, np.float32)
-                    for j in range(1, n):
-                        acc = (acc + np.asarray(slots[j][name], np.float32)).astype(np.float32)
-                    red[name] = (acc * np.float32(1.0 / n)).astype(np.float32)
+                red.update(reduce(slots, n))
             bar.wait()
             return {name: v.copy() for name, v in red.items()}
         return hook
@@ -203,12 +213,7 @@ def oracle_dp_actor_phase(L0, s, n, critic, masks=None):
     b = s.shape[0] // n
     gs = [orc.featured_actor_grads(Lt, s[k * b:(k + 1) * b], masks=masks[k] if masks else None)
           for k in range(n)]
-    red = {}
-    for name in gs[0]:
-        acc = np.asarray(gs[0][name], np.float32)
-        for j in range(1, n):
-            acc = (acc + np.asarray(gs[j][name], np.float32)).astype(np.float32)
-        red[name] = (acc * np.float32(1.0 / n)).astype(np.float32)
+    red = dp_mean(gs, n)
     Lt.adam_actor({k: v.copy() for k, v in red.items()})
     Lt.polyak()
     return Lt, red

@@ -46,6 +46,16 @@ def test_query_route_export(lib):
     assert buf.raw[:63] == b"\xab" * 63
 
 
+def test_last_stage_export(lib):
+    """td3_debug_last_stage (the stage list a replica's step left behind; tests/test_gpu_dp_edges.py) is
+    declared, exported and bound, and answers "" for a null handle."""
+    from td3_amd import _lib
+    assert "td3_debug_last_stage" in _header_symbols()
+    res, args = _lib.SIGNATURES["td3_debug_last_stage"]
+    assert res is C.c_char_p and len(args) == 3
+    assert lib.td3_debug_last_stage(None, 0, 0) == b"" and lib.td3_debug_last_stage(None, 0, 1) == b""
+
+
 def test_no_cpu_fallback_symbols(lib):
     # the product library must not reference the oracle
     data = open(os.path.join(ROOT, "td3_amd", "libtd3hip.so"), "rb").read()

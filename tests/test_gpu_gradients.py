@@ -113,7 +113,13 @@ def _gpu_masks(pol, B, actor_step):
     step backpropagates through: Q1, Q2 (s, a); on a policy step the actor (s) and Q1 (s, pi)."""
     import ctypes as C
     from td3_amd import _lib
-    q, a = [500, 400, 200], [500, 400, 300]
+
+    def hidden(group, prefix):                      # the learner's own widths (custom arch: tests/dp_reference.py)
+        shapes = dict(pol._tensors[group])
+        kind = "weight_v" if f"{prefix}linears.0.weight_v" in shapes else "weight"
+        return [shapes[f"{prefix}linears.{i}.{kind}"][0] for i in range(3)]
+
+    q, a = hidden(1, "q1."), hidden(0, "")
     evals = [("q1", 1, q), ("q2", 2, q)] + ([("actor", 3, a), ("aq", 6, q)] if actor_step else [])
     out = {}
     for name, ev, widths in evals:
