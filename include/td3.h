@@ -46,6 +46,9 @@
  *                        TD3+BC (Fujimoto & Gu 2021; no counterpart in the reference): the behaviour-cloning
  *                        term of the featured actor step, for buffers the learner did not collect
  *                        (experience_injection.py, main.py --load_replay_buffer)
+ *   td3_set_grad_clip / td3_clip_info
+ *                        torch.nn.utils.clip_grad_norm_ between backward() and step() (one line with the
+ *                        reference's torch classes): global-norm clipping of either group's gradient, on device
  *   td3_select_action_particles_device / td3_eval_q_particles_device
  *                        the particle learner's select_action (+ noise + clip) / eval_q on device rows
  *   td3_actor_learn_particles TD3_particles.TD3._actor_learn TD3_particles.py:209-224
@@ -415,7 +418,9 @@ enum td3_which {
   TD3_ACTOR_ADAM_M = 4, TD3_ACTOR_ADAM_V = 5, TD3_CRITIC_ADAM_M = 6, TD3_CRITIC_ADAM_V = 7,
   /* gradient arenas (read only): in data-parallel mode the all-reduced SUM of the replicas' batch-mean
    * gradients of the last phase (divide by nranks for the mean); with weight normalization dL/dW.
-   * Not written by the single-device fused path (its dW tiles feed Adam directly). */
+   * Not written by the single-device fused path (its dW tiles feed Adam directly) -- except for a group
+   * that clips its gradient (td3_set_grad_clip): its arena holds the last step's unclipped batch-mean
+   * gradient. */
   TD3_ACTOR_GRAD = 8, TD3_CRITIC_GRAD = 9
 };
 
@@ -709,6 +714,56 @@ typedef struct td3_bc_info_t {
 } td3_bc_info_t;
 int td3_set_bc(td3_handle* h, double alpha);
 int td3_bc_info(td3_handle* h, td3_bc_info_t* info);
+
+/* ------------------------------------------------------------------ gradient clipping */
+/* torch.nn.utils.clip_grad_norm_ with its defaults (norm_type = 2, error_if_nonfinite = False) between a
+ * group's backward and its Adam step, on one device.  The rule is per group: the critic group is both
+ * twins and, on a particle learner, their encoders (critic.parameters()); the actor group includes its
+ * encoder.  Each optimizer step of a group with max_norm > 0 does
+ *   total = sqrt(sum over every parameter element of g^2)
+ *   coef  = min(1, max_norm / (total + 1e-6))
+ *   Adam sees coef * g
+ * with NO guard for a non-finite total: IEEE arithmetic decides, as in torch (a NaN total gives a NaN coef).
+ * Arithmetic: every fp32 gradient element is widened and squared in fp64 and accumulated in fp64 in one
+ * fixed order that depends on the arena's size alone (DESIGN.md §4b spells it) -- not on the batch, the
+ * launch mode or the dW kernel that produced the gradient; sqrt, the sum with 1e-6, the division and the
+ * min are fp64; coef is rounded to fp32 once and multiplies g in fp32.  No float atomics: runs repeat bit
+ * for bit, and graph replay equals direct launches.  The gradient arena itself is not scaled:
+ * td3_get_params(TD3_*_GRAD) of a clipping group returns the step's unclipped batch-mean gradient.
+ *
+ * A clipping group takes, in place of its fused <tag>_dw stage (tag C / A): <tag>_dw in gradient-only mode
+ * (and <tag>_enc_adam likewise, particles), <tag>_gnorm (one launch: W workgroups, one fp64 partial each)
+ * and <tag>_adam (the flat Adam pass with Polyak and the forward weights' images; every workgroup adds the
+ * W partials in index order and forms coef itself).  A group without clipping keeps its fused stage:
+ * clipping the critic only leaves the actor phase exactly as it is.  A handle never touched, or set back
+ * to 0, runs the same stage list, the same kernels and the same bits as without the feature.
+ * Taken by featured learners with norm None or "layer" and particle learners (CDQ on and off), on every
+ * single-device step entry point, with TD3+BC on or off: td3_train_step, td3_train_step_batch,
+ * td3_train_step_batch_particles, both prioritized steps (the norm is of the weighted gradient),
+ * td3_actor_learn_particles (the actor group), td3_probe_kernel, td3_profile_stages.
+ *
+ * td3_set_grad_clip: group 0 actor, 1 critic (td3_set_adam's convention); max_norm = 0 turns the group's
+ *   clipping off.  It waits for the learner's queued steps.  max_norm lives in a device scalar: changing
+ *   one positive value to another rebuilds nothing (the captured graphs replay unchanged; anneal it
+ *   freely); switching a group on or off rebuilds the step plan and its graphs, as td3_set_bc does.
+ *   Returns -1 with a message, before any GPU work, for (checked in this order): max_norm negative or
+ *   non-finite; group not 0 or 1; a null handle; a weight-normalised learner (norm: its Adam runs on
+ *   dg / dv inside wn_kernel); a handle in a td3_comm_init or td3_comm_init_local group -- and both of
+ *   those refuse a handle with clipping on (the data-parallel form is the norm behind the all-reduce).
+ * td3_clip_info: synchronous like td3_bc_info.  step[g] is total_it of group g's last optimizer step taken
+ *   with clipping in the current step plan (td3_actor_learn_particles does not move total_it and reports
+ *   under the current one), grad_norm[g] that step's total before scaling, coef[g] the float32 factor the
+ *   kernel used, widened.  A plan rebuild forgets the three (0).  Returns -1 for a null info, then a null
+ *   handle.  No other struct changes its layout. */
+typedef struct td3_clip_info_t {
+  int     enabled[2];     /* index = group: 0 actor, 1 critic (td3_set_adam's convention) */
+  double  max_norm[2];
+  int64_t step[2];        /* total_it of the group's last optimizer step taken with clipping in the current plan, 0 if none */
+  double  grad_norm[2];   /* that step's total L2 norm of the group's gradient, before scaling */
+  double  coef[2];        /* the factor applied, as the float32 the kernel used, widened */
+} td3_clip_info_t;
+int td3_set_grad_clip(td3_handle* h, int group, double max_norm);   /* 0 turns the group's clipping off */
+int td3_clip_info(td3_handle* h, td3_clip_info_t* info);
 
 /* ------------------------------------------------------------------ multi-GPU (RCCL) */
 int td3_comm_unique_id(unsigned char out[128]);

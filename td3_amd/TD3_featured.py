@@ -192,16 +192,28 @@ def torch_default_init(sd, ad, norm, actor_arch=ACTOR_ARCH, q_arch=Q_ARCH):
     return actor, critic
 
 
+def _clip_pair(v):
+    """``max_grad_norm`` as [actor, critic] floats (0: off): a float for both groups, or (actor, critic)."""
+    pair = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if len(pair) != 2:
+        raise ValueError("max_grad_norm is a float (both groups) or (actor, critic)")
+    return [0.0 if x is None else float(x) for x in pair]
+
+
 class TD3(TD3_base):
     """TD3_featured.TD3 (TD3_featured.py:99-171) on the HIP pipeline."""
 
     def __init__(self, obs_space, action_space, max_action=1, lr=1e-4, norm=None, CDQ=True,
                  device=None, seed=0, use_graph="auto", actor_arch=ACTOR_ARCH, q_arch=Q_ARCH,
-                 init="torch", bc_alpha=None, **kwargs):
+                 init="torch", bc_alpha=None, max_grad_norm=None, **kwargs):
         super().__init__(max_action=max_action, **kwargs)
         self._lib = _lib.load()
         if norm not in (None, "layer", "weight_normalization"):
             raise ValueError(f"norm={norm!r} is not supported (None, 'layer' or 'weight_normalization')")
+        if norm == "weight_normalization" and any(_clip_pair(max_grad_norm)):
+            # refused before a handle exists (td3_set_grad_clip would refuse it after)
+            raise ValueError("max_grad_norm with norm='weight_normalization' is not supported: its Adam runs on "
+                             "(g, v), not on the weight's gradient")
         self.norm = norm
         self.CDQ = CDQ          # TD3_featured ignores it (always twin critics), :100
         sd, ad = int(obs_space.shape[0]), int(action_space.shape[0])
@@ -245,6 +257,9 @@ class TD3(TD3_base):
         # is bc_alpha / mean |Q|, next to an MSE between the policy's and the stored action (None / 0: off)
         if bc_alpha:
             self.bc_alpha = bc_alpha
+        # torch.nn.utils.clip_grad_norm_ ahead of each group's Adam step: a float, or (actor, critic)
+        if max_grad_norm is not None:
+            self.max_grad_norm = max_grad_norm
 
     # ------------------------------------------------------------------ plumbing
     def _query_tensors(self, g):
@@ -318,6 +333,58 @@ class TD3(TD3_base):
         check(self._lib.td3_bc_info(self._h, C.byref(info)), "td3_bc_info")
         return {"enabled": bool(info.enabled), "alpha": info.alpha, "step": info.step, "lambda": getattr(info, "lambda"),
                 "q_abs_mean": info.q_abs_mean, "bc_loss": info.bc_loss}
+
+    @property
+    def max_grad_norm(self):
+        """The threshold of ``torch.nn.utils.clip_grad_norm_`` applied to each group's gradient ahead of its
+        Adam step (``td3_set_grad_clip``): None when off, a float when both groups share it, else
+        ``(actor, critic)`` with None for a group that does not clip.  Set it to a float (both groups), to
+        ``(actor, critic)``, or to None / 0 (off).  A new positive value costs no plan rebuild (anneal it
+        freely); switching a group on or off rebuilds the step plan."""
+        a, c = getattr(self, "_max_grad_norm", (None, None))
+        if a is None and c is None:
+            return None
+        return a if a == c else (a, c)
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        vals = _clip_pair(v)
+        before = self._clip_thresholds()
+        try:
+            for g, x in enumerate(vals):
+                check(self._lib.td3_set_grad_clip(self._h, g, x), "td3_set_grad_clip")
+        except Exception:
+            # both groups or neither: a value refused for one group leaves the other as it was
+            for g, x in enumerate(before):
+                self._lib.td3_set_grad_clip(self._h, g, x)
+            raise
+        finally:
+            self._max_grad_norm = tuple(x if x > 0 else None for x in self._clip_thresholds())
+
+    def _clip_thresholds(self):
+        """(actor, critic) thresholds as the handle holds them (0: off)."""
+        info = _lib.td3_clip_info_t()
+        check(self._lib.td3_clip_info(self._h, C.byref(info)), "td3_clip_info")
+        return info.max_norm[0], info.max_norm[1]
+
+    def clip_info(self):
+        """``td3_clip_info`` as a dict of ``"actor"`` / ``"critic"`` dicts: ``enabled``, ``max_norm``, ``step``
+        (``total_it`` of the group's last optimizer step taken with clipping, 0 if none), ``grad_norm`` (that
+        step's total L2 norm before scaling) and ``coef`` (the factor applied).  Synchronous."""
+        info = _lib.td3_clip_info_t()
+        check(self._lib.td3_clip_info(self._h, C.byref(info)), "td3_clip_info")
+        return {name: {"enabled": bool(info.enabled[g]), "max_norm": info.max_norm[g], "step": info.step[g],
+                       "grad_norm": info.grad_norm[g], "coef": info.coef[g]}
+                for g, name in enumerate(("actor", "critic"))}
+
+    def _clip_stats(self, out, actor_step):
+        """The clipping keys of a step's stats dict (``train_step(..., stats=True)``)."""
+        if self.max_grad_norm is None:
+            return
+        ci = self.clip_info()
+        for name in ("critic", "actor") if actor_step else ("critic",):
+            if ci[name]["enabled"]:
+                out[f"{name}_grad_norm"], out[f"{name}_clip_coef"] = ci[name]["grad_norm"], ci[name]["coef"]
 
     def set_weights(self, actor, critic, actor_target=None, critic_target=None):
         """Load numpy/torch state dicts; targets default to copies (TD3_featured.py:102,107)."""
@@ -449,7 +516,9 @@ class TD3(TD3_base):
         the device; ``u`` (``[batch_size]`` mass fractions) replaces that draw and the stats gain
         ``"weight"`` and ``"td_abs"``.  With ``bc_alpha`` set, the stats of an actor step gain
         ``"bc_lambda"``, ``"bc_q_abs_mean"``, ``"bc_loss"`` and ``"bc_actor_loss"`` (= -lambda mean Q +
-        bc_loss; ``"actor_loss"`` keeps its meaning, -mean Q)."""
+        bc_loss; ``"actor_loss"`` keeps its meaning, -mean Q).  With ``max_grad_norm`` set, the stats gain
+        ``"critic_grad_norm"`` and ``"critic_clip_coef"``, and on actor steps ``"actor_grad_norm"`` and
+        ``"actor_clip_coef"`` (each for a group that clips)."""
         B = int(batch_size)
         st = None
         keep = []
@@ -521,6 +590,7 @@ class TD3(TD3_base):
                 bi = self.bc_info()
                 out["bc_lambda"], out["bc_q_abs_mean"], out["bc_loss"] = bi["lambda"], bi["q_abs_mean"], bi["bc_loss"]
                 out["bc_actor_loss"] = bi["lambda"] * st.actor_loss + bi["bc_loss"]
+        self._clip_stats(out, bool(st.actor_step))
         if prioritized:
             out["weight"], out["td_abs"] = weight, td_abs
         return out

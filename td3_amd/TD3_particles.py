@@ -81,7 +81,7 @@ class TD3(_FeaturedTD3):
     """TD3_particles.TD3 (TD3_particles.py:135-224) on the HIP pipeline."""
 
     def __init__(self, obs_space, action_space, lr=1e-4, norm=None, CDQ=True, device=None, seed=0,
-                 use_graph="auto", init="torch", per_beta=None, **kwargs):
+                 use_graph="auto", init="torch", per_beta=None, max_grad_norm=None, **kwargs):
         TD3_base.__init__(self, **kwargs)
         # the importance-weight exponent of prioritized steps; None: prioritized rings are refused
         self.per_beta = per_beta
@@ -130,6 +130,9 @@ class TD3(_FeaturedTD3):
         if init == "torch":
             a0, c0 = torch_default_init(F, N, D, A, norm, self.CDQ)
             self.set_weights(a0, c0)
+        # torch.nn.utils.clip_grad_norm_ ahead of each group's Adam step: a float, or (actor, critic)
+        if max_grad_norm is not None:
+            self.max_grad_norm = max_grad_norm
 
     def _query_tensors(self, g):
         out = []
@@ -314,6 +317,7 @@ class TD3(_FeaturedTD3):
                "y": keep[0], "q1": keep[1], "q2": keep[2], "idx": keep[3], "noise": keep[4]}
         if st.actor_step:
             out["actor_loss"] = st.actor_loss
+        self._clip_stats(out, bool(st.actor_step))
         if prioritized:
             out["weight"], out["td_abs"] = weight, td_abs
         return out

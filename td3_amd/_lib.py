@@ -107,6 +107,11 @@ class td3_bc_info_t(C.Structure):
                 ("q_abs_mean", C.c_double), ("bc_loss", C.c_double)]
 
 
+class td3_clip_info_t(C.Structure):
+    _fields_ = [("enabled", C.c_int * 2), ("max_norm", C.c_double * 2), ("step", C.c_int64 * 2),
+                ("grad_norm", C.c_double * 2), ("coef", C.c_double * 2)]
+
+
 class td3_log_info_t(C.Structure):
     _fields_ = [("enabled", C.c_int), ("capacity", C.c_int), ("every", C.c_int), ("count", C.c_int64)]
 
@@ -192,6 +197,8 @@ SIGNATURES = {
     "td3_log_set": (C.c_int, [_P, C.POINTER(td3_log_entry), C.c_int64, C.c_int64]),
     "td3_set_bc": (C.c_int, [_P, C.c_double]),
     "td3_bc_info": (C.c_int, [_P, C.POINTER(td3_bc_info_t)]),
+    "td3_set_grad_clip": (C.c_int, [_P, C.c_int, C.c_double]),
+    "td3_clip_info": (C.c_int, [_P, C.POINTER(td3_clip_info_t)]),
     "td3_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "td3_comm_init": (C.c_int, [_P, C.POINTER(C.c_ubyte), C.c_int, C.c_int]),
     "td3_comm_init_local": (C.c_int, [C.POINTER(_P), C.c_int]),

@@ -53,6 +53,7 @@ int td3_profile_stages(td3_handle* h, rb_handle* rbh, int batch, int actor_phase
   h->critic_step += 1;
   if (actor_phase) h->actor_step += 1;   // (stream synchronised above: no actor event needed)
   note_bc_step(h, actor_phase);
+  note_clip_step(h, actor_phase);
   return 0;
 }
 

@@ -51,7 +51,7 @@ static Stage collective_stage(const td3_handle* h, const std::string& name, cons
 
 // The flat optimizer's image map of a group's forward weights (P4 null when the plan being built does
 // not use the images); `base`: the arena offset of the range it updates
-static int w4_map(const td3_handle* h, const Group& g, int64_t base, W4Map* out) {
+int w4_map(const td3_handle* h, const Group& g, int64_t base, W4Map* out) {
   W4Map w{};
   if (h->w4_build) {
     w.P4 = g.P4;
@@ -321,6 +321,8 @@ int td3_comm_init(td3_handle* h, const unsigned char id[128], int nranks, int ra
   TD3_ARG(nranks >= 1 && rank >= 0 && rank < nranks, "bad rank / nranks");
   TD3_ARG(!h->log, "the training log is enabled on this handle (data-parallel logging is not supported)");
   TD3_ARG(h->bc_alpha == 0.0, "TD3+BC is on for this handle (td3_set_bc): data-parallel BC is not supported");
+  TD3_ARG(h->clip_max[0] == 0.0 && h->clip_max[1] == 0.0,
+          "gradient clipping is on for this handle (td3_set_grad_clip): data-parallel clipping is not supported");
   TD3_HIP(hipSetDevice(h->cfg.device));
   ncclUniqueId uid;
   memcpy(&uid, id, 128);
@@ -351,6 +353,8 @@ int td3_comm_init_local(td3_handle** hs, int n) {
     TD3_ARG(!hs[k]->comm && !hs[k]->local, "handle already in a data-parallel group");
     TD3_ARG(!hs[k]->log, "the training log is enabled on a handle (data-parallel logging is not supported)");
     TD3_ARG(hs[k]->bc_alpha == 0.0, "TD3+BC is on for a handle (td3_set_bc): data-parallel BC is not supported");
+    TD3_ARG(hs[k]->clip_max[0] == 0.0 && hs[k]->clip_max[1] == 0.0,
+            "gradient clipping is on for a handle (td3_set_grad_clip): data-parallel clipping is not supported");
     TD3_ARG(hs[k]->cfg.device == hs[0]->cfg.device, "local replicas share one device");
     TD3_ARG(same_shape(hs[k]->cfg, hs[0]->cfg), "local replicas must have the same configuration");
     for (int j = 0; j < k; ++j) TD3_ARG(hs[j] != hs[k], "a handle appears twice");

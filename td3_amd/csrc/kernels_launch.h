@@ -440,10 +440,13 @@ int launch_dw_split(const DwArgs& a, const DwSplit& k, hipStream_t s) {
   return 0;
 }
 
-int launch_adam_flat(const AdamArgs& a, int64_t n, int polyak, hipStream_t s, const W4Map* w4) {
+// The flat optimizer launches' argument check (launch_adam_flat here, launch_adam_flat_clip in clip.hip): the
+// range float4-aligned, the image map (w4 nullable, or without P4: no images) sound; out: the map to pass, the grid
+int adam_flat_args(const char* who, const AdamArgs& a, int64_t n, int polyak, const W4Map* w4, W4Map* out,
+                   int* blocks) {
   auto al16 = [](const float* p) { return ((uintptr_t)p & 15) == 0; };
   if ((n & 3) || !al16(a.P) || !al16(a.G) || !al16(a.M) || !al16(a.V) || (polyak && !al16(a.T))) {
-    set_error("launch_adam_flat: the range must be float4-aligned (n %% 4 == 0, 16-B aligned arenas)");
+    set_error("%s: the range must be float4-aligned (n %% 4 == 0, 16-B aligned arenas)", who);
     return -1;
   }
   W4Map w{};
@@ -452,11 +455,19 @@ int launch_adam_flat(const AdamArgs& a, int64_t n, int polyak, hipStream_t s, co
     bool ok = w.nmat >= 1 && w.nmat <= 8 && (w.base & 3) == 0 && (!polyak || w.T4);
     for (int m = 0; ok && m < w.nmat; ++m) ok = (w.off[m] & 3) == 0 && w.Kp[m] % 4 == 0;
     if (!ok) {
-      set_error("launch_adam_flat: bad k-quad image map");
+      set_error("%s: bad k-quad image map", who);
       return -1;
     }
   }
-  const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256, 2048);
+  *out = w;
+  *blocks = (int)std::min<int64_t>((n / 4 + 255) / 256, 2048);
+  return 0;
+}
+
+int launch_adam_flat(const AdamArgs& a, int64_t n, int polyak, hipStream_t s, const W4Map* w4) {
+  W4Map w;
+  int blocks;
+  TD3_RC(adam_flat_args("launch_adam_flat", a, n, polyak, w4, &w, &blocks));
   hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks), dim3(256), 0, s, a, n, polyak, w);
   TD3_HIP(hipGetLastError());
   return 0;

@@ -1,5 +1,5 @@
 // Internal header of the learner's translation units (td3.hip, stages.hip, step.hip, act.hip, dp.hip,
-// debug.hip, trainlog.hip): the types they share and the functions that cross a file boundary.  Functions used in
+// debug.hip, trainlog.hip, clip.hip): the types they share and the functions that cross a file boundary.  Functions used in
 // one file are static there.
 #pragma once
 #include <rccl/rccl.h>
@@ -319,6 +319,18 @@ struct TrainLog {
   const Plan* last_plan = nullptr;
 };
 
+// Global-norm gradient clipping (include/td3.h, "gradient clipping"; clip.hip): one group's device state.
+// The setter writes max_norm; the group's gnorm stage writes the partials; its Adam stage writes
+// (total, coef) of the step for td3_clip_info.
+constexpr int kClipMaxWg = 128;
+struct ClipDev {
+  double max_norm;
+  double total;
+  double partial[kClipMaxWg];
+  float coef;
+  float pad_;
+};
+
 struct EncItem {
   const NetL* net;
   const float* P;         // group arena (encoder at P + net->enc_off)
@@ -392,6 +404,13 @@ struct td3_handle {
   // the current plan (0: none; the plan holds that step's lambda and row errors)
   double bc_alpha = 0.0;
   int64_t bc_step = 0;
+  // Gradient clipping (td3_set_grad_clip), index = group (0 actor, 1 critic): the threshold (0: off), its
+  // device state (allocated by the first call that turns a group on), and total_it of the group's last
+  // optimizer step taken with clipping in the current plan (clip_has: there is one to report)
+  double clip_max[2] = {0.0, 0.0};
+  td3::ClipDev* d_clip = nullptr;
+  int64_t clip_step[2] = {0, 0};
+  bool clip_has[2] = {false, false};
 };
 
 namespace td3 {
@@ -479,6 +498,19 @@ int check_ring(const td3_handle* h, const Ring* r, RingUser what);
 inline void note_bc_step(td3_handle* h, int actor_phase) {
   if (actor_phase && h->plan && h->plan->bc) h->bc_step = h->total_it;
 }
+// ---- clip.hip
+// whether the group `which` steps (AdamArgs::which: 0 critic, 1 actor) clips its gradient
+inline bool clip_on(const td3_handle* h, int which) { return h->clip_max[which == 1 ? 0 : 1] > 0.0; }
+// the host's note of a step just queued (td3_clip_info's `step`): the critic group steps every time
+inline void note_clip_step(td3_handle* h, int actor_phase) {
+  for (int g = 0; g < 2; ++g)
+    if (h->clip_max[g] > 0.0 && (g == 1 || actor_phase)) {
+      h->clip_step[g] = h->total_it;
+      h->clip_has[g] = true;
+    }
+}
+int add_clip_optimizer(td3_handle* h, std::vector<Stage>& st, Group& g, const AdamArgs& adam, bool polyak,
+                       const char* tag);
 // ---- trainlog.hip
 int log_step(td3_handle* h, int actor_phase, bool prioritized, hipStream_t s);
 void destroy_train_log(td3_handle* h);
@@ -491,6 +523,7 @@ bool dp_buckets(const td3_handle* h, const Group& g, const std::vector<BwdItem>&
 int add_dp_overlapped(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
                       const char* tag, const DwOpts& o, const DwWork& w);
 int add_dp_optimizer(td3_handle* h, std::vector<Stage>& st, Group& g, AdamArgs adam, bool polyak, const char* tag);
+int w4_map(const td3_handle* h, const Group& g, int64_t base, W4Map* out);
 int gather_moments_for_rebuild(td3_handle* h);
 int consolidate_moments(td3_handle* h, int which);
 

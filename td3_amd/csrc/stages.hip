@@ -825,8 +825,10 @@ static int make_dw_work(const StageCtx& c, const Group& g, const std::vector<Bwd
   a.Bp = Bp;
   TD3_ARG(!h->w4_build || (g.P4 && g.T4), "internal: k-quad images not allocated");
   a.adam = group_adam(h, g, o.which);
-  // data parallel and weight normalization (dW -> (dg, dv) in wn_kernel): the gradient only
-  a.mode = (h->comm || h->local || g.wn.nlin > 0) ? kDwGrad : o.polyak ? kDwAdamPolyak : kDwAdam;
+  // data parallel, weight normalization (dW -> (dg, dv) in wn_kernel) and a clipping group (the norm
+  // needs the whole gradient before the first Adam update): the gradient only
+  const bool grad_only = h->comm || h->local || g.wn.nlin > 0 || clip_on(h, o.which);
+  a.mode = grad_only ? kDwGrad : o.polyak ? kDwAdamPolyak : kDwAdam;
   // a launch's algorithmic bytes: gradient-only dW writes 4 B per parameter; the fused Adam reads and
   // writes P, M, V (24 B; the gradient never leaves registers), Polyak reads and writes T (+8 B), and
   // the k-quad images take every updated weight once more (+4 B, +4 B more for T4 on Polyak steps)
@@ -913,7 +915,8 @@ int push_wn_stage(std::vector<Stage>& st, const Group& g, const AdamArgs& adam, 
 
 // Weight / bias / LN grads of every layer of `items` (o.enc_nwg, TD3_particles: then the encoders'),
 // then the optimizer step: fused into the dW launch on one GPU; wn_kernel under weight normalization;
-// in a data-parallel plan the dW kernels write the gradient only and dp.hip's schedule follows.
+// in a data-parallel plan the dW kernels write the gradient only and dp.hip's schedule follows; so they do
+// for a group that clips its gradient (td3_set_grad_clip), and clip.hip's norm and Adam stages follow.
 int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std::vector<BwdItem>& items,
                  const char* tag, const DwOpts& o) {
   DwWork w;
@@ -923,6 +926,7 @@ int add_dw_stage(const StageCtx& c, std::vector<Stage>& st, Group& g, const std:
   TD3_RC(push_dw_stage(c, st, w, o.slab, std::string(tag) + "_dw"));
   if (o.enc_nwg > 0) TD3_RC(push_enc_adam_stage(st, items, w, o.enc_nwg, tag));
   if (dp) return add_dp_optimizer(c.h, st, g, w.a.adam, o.polyak, tag);
+  if (clip_on(c.h, o.which)) return add_clip_optimizer(c.h, st, g, w.a.adam, o.polyak, tag);
   if (g.wn.nlin > 0) return push_wn_stage(st, g, w.a.adam, o.polyak, tag);
   return 0;
 }

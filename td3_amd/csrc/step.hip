@@ -862,6 +862,10 @@ static int run_body(td3_handle* h, int actor_phase, int inj, hipStream_t s, Ring
 int build_plan(td3_handle* h, int B) {
   const bool was_sharded = h->dp_sharded && h->nranks > 1;
   h->bc_step = 0;                             // the last BC step's lambda / row errors go with the plan
+  for (int g = 0; g < 2; ++g) {               // and the last clipped steps' norm / coef
+    h->clip_step[g] = 0;
+    h->clip_has[g] = false;
+  }
   h->dp_sharded = false;                      // set again by dp.hip add_dp_sharded
   // the profiled stage list lives in the plan being replaced
   h->last_body = nullptr;
@@ -929,6 +933,7 @@ int finish_step(td3_handle* h, int actor_phase, hipStream_t s, td3_step_stats* s
   // the training log's launch: behind the body (and a prioritized step's write-back), ahead of the sync
   if (h->log && h->total_it % h->log->every == 0) TD3_RC(log_step(h, actor_phase, prioritized, s));
   note_bc_step(h, actor_phase);
+  note_clip_step(h, actor_phase);
   if (!stats) return 0;
   Plan* P = h->plan.get();
   TD3_HIP(hipStreamSynchronize(s));
@@ -1169,6 +1174,10 @@ int td3_actor_learn_particles(td3_handle* h, const float* feat, const float* par
   h->last_step_stream = s;
   h->actor_step += 1;
   TD3_RC(note_actor_update(h, s));
+  if (h->clip_max[0] > 0.0) {                 // total_it does not move: the call reports under the current one
+    h->clip_step[0] = h->total_it;
+    h->clip_has[0] = true;
+  }
   if (!actor_loss) return 0;
   TD3_HIP(hipStreamSynchronize(s));
   const int nq = P->nq, ldq = P->ldq;

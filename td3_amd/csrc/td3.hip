@@ -291,6 +291,7 @@ int td3_destroy(td3_handle* h) {
   (void)hipFree(h->arena);
   (void)hipFree(h->d_ctr);
   (void)hipFree(h->ones);
+  if (h->d_clip) (void)hipFree(h->d_clip);
   (void)hipStreamSynchronize(h->act_stream);
   (void)hipStreamDestroy(h->act_stream);
   if (h->actor_ev) (void)hipEventDestroy(h->actor_ev);
