@@ -46,6 +46,10 @@
  *                        TD3+BC (Fujimoto & Gu 2021; no counterpart in the reference): the behaviour-cloning
  *                        term of the featured actor step, for buffers the learner did not collect
  *                        (experience_injection.py, main.py --load_replay_buffer)
+ *   td3_train_step_mixed
+ *                        demonstration replay (DDPGfD / RLPD symmetric sampling; the online half of
+ *                        experience_injection.py + main.py --load_replay_buffer): every batch draws a fixed
+ *                        number of rows from a demonstration ring and the rest from the online ring
  *   td3_set_grad_clip / td3_clip_info
  *                        torch.nn.utils.clip_grad_norm_ between backward() and step() (one line with the
  *                        reference's torch classes): global-norm clipping of either group's gradient, on device
@@ -714,6 +718,44 @@ typedef struct td3_bc_info_t {
 } td3_bc_info_t;
 int td3_set_bc(td3_handle* h, double alpha);
 int td3_bc_info(td3_handle* h, td3_bc_info_t* info);
+
+/* ------------------------------------------------------------------ Demonstration replay (two rings) */
+/* One TD3.train step of either learner kind, on one device, whose batch rows [0, n_demo) come from the
+ * ring `demo` and rows [n_demo, batch) from the ring `rb` ("symmetric sampling": Vecerik et al. 2017,
+ * DDPGfD; Ball et al. 2023, RLPD).  The reference's workflow it serves: a buffer filled from a recorded
+ * policy (experience_injection.py) kept as `demo`, and online training on top of it (main.py
+ * --load_replay_buffer) adding to `rb`, so the demonstrations' share of a batch neither decays nor is
+ * overwritten by the FIFO.  Both rings have the learner's kind and dims, hence one record layout.
+ *
+ * The draw of batch row r is uniform on r's own ring: philox_index(seed of that ring, total_it + 1, r,
+ * size of that ring) -- td3_train_step's draw with the batch row as counter on both sides.  n_demo = 0 is
+ * td3_train_step's draw on `rb`, n_demo = batch its draw on `demo`, and both equal that step bit for bit.
+ * One input launch (csrc/mixed.hip) fills the plan's batch buffers from both rings -- for a particle
+ * learner also the packed particle rows [Bp][2 N D] (s | s') its encoders then read, as in
+ * td3_train_step_batch_particles -- and the step's body is the one of the injected-index steps.  n_demo
+ * is an argument of that launch alone: it may change every step with no plan rebuild and no re-capture.
+ *
+ * inject_idx: host [batch], nullable; its first n_demo entries index `demo`, the rest `rb`, each checked
+ *   against its ring's capacity.  inject_noise, stats (stats->idx: the drawn rows, each in its own ring),
+ *   the host synchronisations they force, the counters, the training log (prioritized = 0), TD3+BC (its
+ *   term covers every row of the batch) and gradient clipping are td3_train_step's.
+ * Ordering: the step is ordered after every add queued on either ring before it, and adds to either ring
+ *   queued after it wait for its reads (one read section on `rb`, then `demo`).
+ * Mixing step kinds: a mixed step after a prioritized one refills unit weights; a plain or prioritized
+ *   step after a mixed one is bit for bit what it would have been (a particle learner's encoders switch
+ *   back to the ring, as after td3_train_step_batch_particles).
+ * Returns -1 with a message, before any GPU work and leaving the counters and both rings' ordering state
+ *   unchanged, for (checked in this order): batch <= 0; n_demo outside [0, batch]; a null h, rb or demo;
+ *   rb == demo; a ring whose kind, dims, particle shape or device do not match the learner (rb, then
+ *   demo); priorities enabled on either ring (the mixed draw is uniform); a handle in a td3_comm_init /
+ *   td3_comm_init_local group; a ring that contributes at least one row being empty while inject_idx is
+ *   null (a ring that contributes no row may be empty); an injected index outside its ring.
+ * td3_debug_mixed_input: re-queues the last mixed step's input launch on the rows that step read
+ *   (measurement); -1 unless the handle's last step was a mixed step on these two rings in the current
+ *   step plan.  No struct layout changes. */
+int td3_train_step_mixed(td3_handle* h, rb_handle* rb, rb_handle* demo, int batch, int n_demo, void* stream,
+                         const int64_t* inject_idx, const float* inject_noise, td3_step_stats* stats);
+int td3_debug_mixed_input(td3_handle* h, rb_handle* rb, rb_handle* demo, void* stream);  /* re-queue the last mixed step's input launch (measurement) */
 
 /* ------------------------------------------------------------------ gradient clipping */
 /* torch.nn.utils.clip_grad_norm_ with its defaults (norm_type = 2, error_if_nonfinite = False) between a

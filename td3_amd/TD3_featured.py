@@ -31,7 +31,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .TD3_base import TD3_base
-from .my_replay_buffer import ReplayBuffer_featured, default_device_index
+from .my_replay_buffer import MixedReplay, ReplayBuffer_featured, default_device_index
 
 ACTOR_ARCH = (500, 400, 300)   # TD3_featured.py:19
 Q_ARCH = (500, 400, 200)       # TD3_featured.py:54
@@ -510,7 +510,10 @@ class TD3(TD3_base):
         self.train_step(replay_buffer, batch_size)
 
     def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False, u=None):
-        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back.  On a
+        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back.  Given a
+        ``MixedReplay`` the step draws ``n_demo`` rows from its demo ring and the rest from its online ring on
+        the device (``td3_train_step_mixed``); ``indices`` is then ``[batch_size]`` (split by ``n_demo``) or a
+        pair ``(idx_demo, idx_online)`` whose lengths fix ``n_demo``, and the stats gain ``"n_demo"``.  On a
         prioritized ring (``enable_priorities``) without ``indices`` the step draws its rows by
         priority, weights the critic loss with ``per_beta`` and writes the new priorities back, all on
         the device; ``u`` (``[batch_size]`` mass fractions) replaces that draw and the stats gain
@@ -554,6 +557,16 @@ class TD3(TD3_base):
                                                        C.byref(st) if st is not None else None,
                                                        C.byref(per) if per is not None else None),
                   "td3_train_step_prioritized")
+        elif isinstance(replay_buffer, MixedReplay):
+            # demonstration replay: both rings' staged rows in the step's stream order, one input launch
+            replay_buffer.flush(self._lib.td3_stream(self._h))
+            n_demo, ix = replay_buffer._split_indices(B, indices)
+            check(self._lib.td3_train_step_mixed(self._h, replay_buffer.online.handle, replay_buffer.demo.handle,
+                                                 B, n_demo, self._stream(),
+                                                 _lib.i64ptr(ix) if ix is not None else None,
+                                                 _lib.fptr(nz) if nz is not None else None,
+                                                 C.byref(st) if st is not None else None),
+                  "td3_train_step_mixed")
         elif isinstance(replay_buffer, ReplayBuffer_featured):
             replay_buffer.flush(self._lib.td3_stream(self._h))   # in the step's stream order
             ix = None
@@ -593,6 +606,8 @@ class TD3(TD3_base):
         self._clip_stats(out, bool(st.actor_step))
         if prioritized:
             out["weight"], out["td_abs"] = weight, td_abs
+        if isinstance(replay_buffer, MixedReplay):
+            out["n_demo"] = n_demo
         return out
 
     # ------------------------------------------------------------------ training log

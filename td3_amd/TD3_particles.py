@@ -28,7 +28,7 @@ from ._lib import check
 from .TD3_featured import TD3 as _FeaturedTD3
 from .TD3_featured import _AdamView, _ParamView, _torch
 from .TD3_base import TD3_base
-from .my_replay_buffer import ReplayBuffer_particles, default_device_index
+from .my_replay_buffer import MixedReplay, ReplayBuffer_particles, default_device_index
 
 ARCH = (500, 400, 300)      # TD3_particles.py:25 / :76
 NUM_FEATURES = 128          # :27
@@ -248,7 +248,10 @@ class TD3(_FeaturedTD3):
         return float(loss.value) if stats else None
 
     def train_step(self, replay_buffer, batch_size=100, indices=None, noise=None, stats=False, u=None):
-        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back.  With
+        """``train`` with optional injected sample indices / N(0,1) noise and loss read-back.  Given a
+        ``MixedReplay`` the step draws ``n_demo`` rows from its demo ring and the rest from its online ring on
+        the device (``td3_train_step_mixed``); ``indices`` is then ``[batch_size]`` (split by ``n_demo``) or a
+        pair ``(idx_demo, idx_online)`` whose lengths fix ``n_demo``, and the stats gain ``"n_demo"``.  With
         ``per_beta`` set, on a prioritized ring (``enable_priorities``) without ``indices`` the step draws
         its rows by priority, weights the critic loss (one weight per transition, shared by its Q
         outputs) and writes the new priorities back, all on the device; ``u`` (``[batch_size]`` mass
@@ -287,6 +290,16 @@ class TD3(_FeaturedTD3):
                 _lib.fptr(uu) if uu is not None else None, _lib.fptr(nz) if nz is not None else None,
                 C.byref(st) if st is not None else None, C.byref(per) if per is not None else None),
                 "td3_train_step_prioritized_particles")
+        elif isinstance(replay_buffer, MixedReplay):
+            # demonstration replay: both rings' staged rows in the step's stream order, one input launch
+            replay_buffer.flush(self._lib.td3_stream(self._h))
+            n_demo, ix = replay_buffer._split_indices(B, indices)
+            check(self._lib.td3_train_step_mixed(self._h, replay_buffer.online.handle, replay_buffer.demo.handle,
+                                                 B, n_demo, self._stream(),
+                                                 _lib.i64ptr(ix) if ix is not None else None,
+                                                 _lib.fptr(nz) if nz is not None else None,
+                                                 C.byref(st) if st is not None else None),
+                  "td3_train_step_mixed")
         elif isinstance(replay_buffer, ReplayBuffer_particles):
             replay_buffer.flush(self._lib.td3_stream(self._h))   # in the step's stream order
             ix = None
@@ -320,4 +333,6 @@ class TD3(_FeaturedTD3):
         self._clip_stats(out, bool(st.actor_step))
         if prioritized:
             out["weight"], out["td_abs"] = weight, td_abs
+        if isinstance(replay_buffer, MixedReplay):
+            out["n_demo"] = n_demo
         return out

@@ -218,6 +218,9 @@ SIGNATURES = {
     "td3_debug_activation": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "td3_debug_plan_flags": (C.c_int, [_P, _P]),
     "td3_debug_per_stage": (C.c_int, [_P, _P, C.c_int, _P]),
+    "td3_train_step_mixed": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _I64, _F,
+                                       C.POINTER(td3_step_stats)]),
+    "td3_debug_mixed_input": (C.c_int, [_P, _P, _P, _P]),
     "td3_debug_log_launch": (C.c_int, [_P, _P]),
     "td3_debug_row_lds": (C.c_int, []),
     "td3_debug_act_fail": (C.c_int, [_P, C.c_int]),

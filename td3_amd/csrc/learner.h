@@ -168,6 +168,11 @@ struct Plan {
   // the prioritized step combines them into per_td (per_td_combine_kernel)
   float* per_tdj = nullptr;
   uint64_t per_ring_gen = 0;            // Ring::gen of the last prioritized step's ring (d_inject_idx holds its rows)
+  // the last mixed step (td3_train_step_mixed): Ring::gen of its online and demo rings, its n_demo and
+  // total_it after it (any later step moves total_it on); d_idx holds its rows
+  uint64_t mixed_gen[2] = {0, 0};
+  int mixed_n_demo = 0;
+  int64_t mixed_it = 0;
   EvalB TA, Q[2], A, TQ[2], AQ;
   // device problem tables (owned)
   std::vector<void*> tables;

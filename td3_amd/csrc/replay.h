@@ -126,6 +126,31 @@ struct GatherArgs {
 
 int launch_gather(const GatherArgs& a, hipStream_t s);
 
+// The mixed input launch (mixed.hip; include/td3.h "Demonstration replay"): batch rows [0, n_demo)
+// from side 0, rows [n_demo, B) from side 1, each drawn as gather_row_index draws it on its own ring
+// (the batch row is the Philox counter on both sides), rows [B, Bp) zero.  Both rings share the
+// record layout (rec and the segments' src columns).  pbatch (particle learners, else null): the
+// record's two particle blocks [o_p, o_p + np) and [o_p2, o_p2 + np) go to pbatch[row][2 np] as s | s'.
+constexpr int kMixedSegs = kMaxSegs + 2;   // a staged particle record's blocks travel as two more segments
+struct MixedSide {
+  const float* data;
+  const int64_t* d_size;
+  uint64_t seed;
+};
+struct MixedArgs {
+  GatherSeg seg[kMixedSegs];
+  int nseg;
+  int B, Bp, n_demo;
+  int rec;
+  MixedSide side[2];
+  const int64_t* inject_idx;    // nullable: [B], the first n_demo rows of side 0, the rest of side 1
+  int64_t* idx_out;             // nullable
+  const Counters* ctr;          // Philox step = ctr->total_it + 1
+  float* pbatch;
+  int np, o_p, o_p2;
+};
+int launch_mixed_gather(const MixedArgs& a, hipStream_t s);
+
 // The prioritized draw of `batch` rows on `s` (rb_sample_prioritized, include/td3.h): the rows into
 // idx_out and idx_out2 (nullable), the importance weights, normalised by the batch maximum, into
 // weight_out.  inject_u: device, nullable.  The caller holds the ring's read section and has checked

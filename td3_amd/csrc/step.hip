@@ -753,6 +753,48 @@ static int input_from_ring_particles(td3_handle* h, Ring* r, Plan* P, bool injec
   return launch_gather(a, s);
 }
 
+// The mixed step's input (mixed.hip): the destinations of input_from_ring / input_from_ring_particles,
+// filled from two rings of one record layout in one launch; a particle learner's blocks go to pbatch.
+static int input_from_rings(td3_handle* h, Ring* r, Ring* demo, Plan* P, int n_demo, const int64_t* inject_idx,
+                            hipStream_t s) {
+  MixedArgs a{};
+  a.B = P->B;
+  a.Bp = P->Bp;
+  a.n_demo = n_demo;
+  a.rec = r->rec;
+  a.side[0] = MixedSide{demo->data, demo->d_size, demo->seed};
+  a.side[1] = MixedSide{r->data, r->d_size, r->seed};
+  a.inject_idx = inject_idx;
+  a.idx_out = P->d_idx;
+  a.ctr = h->d_ctr;
+  const int sd = h->sd, ad = h->ad;
+  int k = 0;
+  if (P->particles) {
+    const int F = sd, c0 = kEncC2;
+    a.seg[k++] = GatherSeg{P->XA, P->ld_a, c0, r->o_s, F};
+    a.seg[k++] = GatherSeg{P->XAQ, P->ld_q, c0, r->o_s, F};
+    a.seg[k++] = GatherSeg{P->XTA, P->ld_a, c0, r->o_s2, F};
+    for (int j = 0; j < (h->cdq ? 2 : 1); ++j) {
+      a.seg[k++] = GatherSeg{P->XQ[j], P->ld_q, c0, r->o_s, F};
+      a.seg[k++] = GatherSeg{P->XQ[j], P->ld_q, c0 + F, r->o_a, ad};
+      a.seg[k++] = GatherSeg{P->XTQ[j], P->ld_q, c0, r->o_s2, F};
+    }
+    a.pbatch = P->pbatch;
+    a.np = h->N * h->D;
+    a.o_p = r->o_p;
+    a.o_p2 = r->o_p2;
+  } else {
+    a.seg[k++] = GatherSeg{P->X_SA, P->ld_sa, 0, r->o_s, sd};
+    a.seg[k++] = GatherSeg{P->X_SA, P->ld_sa, sd, r->o_a, ad};
+    a.seg[k++] = GatherSeg{P->X_SP, P->ld_sa, 0, r->o_s, sd};
+    a.seg[k++] = GatherSeg{P->X_S2A, P->ld_sa, 0, r->o_s2, sd};
+  }
+  a.seg[k++] = GatherSeg{P->R, 1, 0, r->o_r, 1};
+  a.seg[k++] = GatherSeg{P->ND, 1, 0, r->o_nd, 1};
+  a.nseg = k;
+  return launch_mixed_gather(a, s);
+}
+
 static int input_from_batch(td3_handle* h, Plan* P, const float* s, const float* a, const float* s2,
                             const float* r, const float* nd, hipStream_t st) {
   const int sd = h->sd, ad = h->ad, Bp = P->Bp, B = P->B;
@@ -1075,6 +1117,71 @@ int td3_debug_per_stage(td3_handle* h, rb_handle* rbh, int stage, void* stream) 
   TD3_RC(ring_begin_read(r, s));
   TD3_RC(input_from_ring(h, r, P, true, s));
   return ring_end_read(r, s);
+}
+
+// Demonstration replay: batch rows [0, n_demo) from `demo`, the rest from `rb`, drawn uniformly on
+// each ring; one input launch (mixed.hip), then the non-ring body of the injected-index steps.
+int td3_train_step_mixed(td3_handle* h, rb_handle* rbh, rb_handle* demoh, int batch, int n_demo, void* stream,
+                         const int64_t* inject_idx, const float* inject_noise, td3_step_stats* stats) {
+  TD3_ARG(batch > 0, "batch must be positive");
+  TD3_ARG(n_demo >= 0 && n_demo <= batch, "n_demo must be in [0, batch]");
+  TD3_ARG(h && rbh && demoh, "null handle");
+  TD3_ARG(rbh != demoh, "rb and demo are the same ring (a mixed step draws from two rings)");
+  Ring* r = reinterpret_cast<Ring*>(rbh);
+  Ring* d = reinterpret_cast<Ring*>(demoh);
+  TD3_RC(check_ring(h, r, kLearnerStep));
+  TD3_RC(check_ring(h, d, kLearnerStep));
+  TD3_ARG(!r->pri.on && !d->pri.on,
+          "priorities are enabled on a ring of a mixed step (the mixed draw is uniform)");
+  TD3_ARG(!h->comm && !h->local, "td3_train_step_mixed on a data-parallel handle (comm group attached)");
+  TD3_ARG(inject_idx || ((n_demo == 0 || d->size > 0) && (n_demo == batch || r->size > 0)),
+          "train on an empty replay buffer (a ring that contributes rows to the mixed batch is empty)");
+  if (inject_idx)
+    for (int i = 0; i < batch; ++i)
+      TD3_ARG(inject_idx[i] >= 0 && inject_idx[i] < (i < n_demo ? d->cap : r->cap), "injected index out of range");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_RC(ensure_plan(h, batch));
+  Plan* P = h->plan.get();
+  if (P->particles) {                            // the encoders read the packed batch, not a ring
+    const int np = h->N * h->D;
+    set_particle_source(P, kBatchSource, P->pbatch, 2 * np, 0, np, P->d_iota);
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  TD3_RC(ring_begin_read(r, s));                 // the adds queued on either ring before this step
+  TD3_RC(ring_begin_read(d, s));
+  if (inject_idx)
+    TD3_HIP(hipMemcpyAsync(P->d_inject_idx, inject_idx, (size_t)batch * 8, hipMemcpyHostToDevice, s));
+  if (inject_noise)
+    TD3_HIP(hipMemcpyAsync(P->noise, inject_noise, (size_t)batch * h->ad * 4, hipMemcpyHostToDevice, s));
+  const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
+  TD3_RC(input_from_rings(h, r, d, P, n_demo, inject_idx ? P->d_inject_idx : nullptr, s));
+  TD3_RC(run_body(h, actor_phase, inject_noise ? 1 : 0, s, nullptr));
+  TD3_RC(ring_end_read(r, s));                   // later adds to either ring wait for this step's reads
+  TD3_RC(ring_end_read(d, s));
+  if (inject_idx || inject_noise) TD3_HIP(hipStreamSynchronize(s));   // host sources are pageable
+  TD3_RC(finish_step(h, actor_phase, s, stats));
+  P->mixed_gen[0] = r->gen;
+  P->mixed_gen[1] = d->gen;
+  P->mixed_n_demo = n_demo;
+  P->mixed_it = (int64_t)h->total_it;
+  return 0;
+}
+
+int td3_debug_mixed_input(td3_handle* h, rb_handle* rbh, rb_handle* demoh, void* stream) {
+  TD3_ARG(h && rbh && demoh, "null handle");
+  Ring* r = reinterpret_cast<Ring*>(rbh);
+  Ring* d = reinterpret_cast<Ring*>(demoh);
+  Plan* P = h->plan.get();
+  TD3_ARG(P && P->mixed_it != 0 && P->mixed_it == (int64_t)h->total_it && ring_alive(r, P->mixed_gen[0]) &&
+              ring_alive(d, P->mixed_gen[1]),
+          "run a mixed step on these two rings first (the plan's buffers hold its rows)");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  TD3_RC(ring_begin_read(r, s));
+  TD3_RC(ring_begin_read(d, s));
+  TD3_RC(input_from_rings(h, r, d, P, P->mixed_n_demo, P->d_idx, s));   // the rows of that step again
+  TD3_RC(ring_end_read(r, s));
+  return ring_end_read(d, s);
 }
 
 int td3_train_step_prioritized(td3_handle* h, rb_handle* rbh, int batch, double beta, void* stream,

@@ -25,6 +25,7 @@ writes the fp32 ring (float64(float32(x))).  The fp32 ring stays the training co
 """
 from __future__ import annotations
 
+import math
 import os
 import pickle
 
@@ -658,3 +659,106 @@ class ReplayBuffer_particles(_RingBuffer):
 
 # The reference's module-level alias used by main.py:204-208.
 ReplayBuffer = ReplayBuffer_featured
+
+
+class MixedReplay(object):
+    """Demonstration replay ("symmetric sampling": DDPGfD, RLPD): two device rings of one kind and
+    dims, ``demo`` holding demonstrations (``experience_injection.py``'s rows, a ``--load_replay_buffer``
+    folder) and ``online`` the rows the learner collects.  Every batch draws ``n_demo(batch)`` rows
+    from ``demo`` and the rest from ``online``, so the demonstrations' share neither decays with the
+    online ring's fill nor ends when a FIFO overwrites them.  ``TD3.train`` / ``train_step`` given a
+    ``MixedReplay`` take the step on the device (``td3_train_step_mixed``: one input launch reads both
+    rings); everything that adds rows forwards to ``online``, so ``DeviceTrainLoop`` / ``TrainLoop``
+    take one unchanged.  ``demo_fraction`` is a plain attribute in [0, 1]: anneal it between steps."""
+
+    prioritized = False
+
+    def __init__(self, online, demo, demo_fraction=0.5):
+        for name, ring in (("online", online), ("demo", demo)):
+            if not isinstance(ring, (ReplayBuffer_featured, ReplayBuffer_particles)):
+                raise ValueError(f"MixedReplay: {name} must be a ReplayBuffer_featured or ReplayBuffer_particles")
+        if type(online) is not type(demo):
+            raise ValueError("MixedReplay: online and demo must be rings of the same kind")
+        if online is demo:
+            raise ValueError("MixedReplay: online and demo must be two rings")
+        if tuple(online._dims()) != tuple(demo._dims()):
+            raise ValueError(f"MixedReplay: ring dims differ (online {tuple(online._dims())}, "
+                             f"demo {tuple(demo._dims())})")
+        if online.device != demo.device:
+            raise ValueError("MixedReplay: the rings live on different devices")
+        if online.prioritized or demo.prioritized:
+            raise ValueError("MixedReplay: a prioritized ring (enable_priorities): the mixed draw is uniform")
+        self.online, self.demo = online, demo
+        self.demo_fraction = demo_fraction
+        self.device = online.device
+
+    # ------------------------------------------------------------------ the batch split
+    def n_demo(self, batch):
+        return mixed_n_demo(int(batch), self.demo_fraction, self.online.size, self.demo.size)
+
+    def _split_indices(self, batch, indices):
+        """``(n_demo, idx[batch] or None)`` of a step: ``indices`` None (the device draws), an array
+        ``[batch]`` split by ``n_demo(batch)``, or a pair ``(idx_demo, idx_online)`` whose lengths fix it."""
+        B = int(batch)
+        if indices is None:
+            return self.n_demo(B), None
+        if isinstance(indices, tuple) and len(indices) == 2:
+            d, o = (np.asarray(x, dtype=np.int64).reshape(-1) for x in indices)
+            if d.size + o.size != B:
+                raise ValueError(f"indices: {d.size} demo + {o.size} online rows for a batch of {B}")
+            return int(d.size), np.ascontiguousarray(np.concatenate([d, o]))
+        return self.n_demo(B), np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(B))
+
+    def sample(self, batch_size):
+        """``demo.sample(n_demo)`` followed by ``online.sample(batch - n_demo)``, field by field: what a
+        foreign learner (the reference's own ``TD3``) trains on."""
+        torch = _torch()
+        B = int(batch_size)
+        nd = self.n_demo(B)
+        parts = ([self.demo.sample(nd)] if nd else []) + ([self.online.sample(B - nd)] if B - nd else [])
+        return tuple(torch.cat(f, dim=0) for f in zip(*parts))
+
+    # ------------------------------------------------------------------ forwarded to the online ring
+    def add(self, *a, **k):
+        return self.online.add(*a, **k)
+
+    def add_batch(self, *a, **k):
+        return self.online.add_batch(*a, **k)
+
+    def add_batch_hindsight(self, *a, **k):
+        return self.online.add_batch_hindsight(*a, **k)
+
+    def add_batch_nstep(self, *a, **k):
+        return self.online.add_batch_nstep(*a, **k)
+
+    def flush(self, stream=None):
+        self.online.flush(stream)
+        self.demo.flush(stream)
+
+    @property
+    def size(self):
+        return self.online.size
+
+    @property
+    def ptr(self):
+        return self.online.ptr
+
+    def save(self, folder):
+        """The online ring in the reference's layout (the demonstrations have their own folder)."""
+        return self.online.save(folder)
+
+
+def mixed_n_demo(batch, demo_fraction, online_size, demo_size):
+    """Rows of a ``batch`` a ``MixedReplay`` draws from its demo ring: ``floor(batch * demo_fraction + 0.5)``
+    capped at ``batch``; 0 while the demo ring is empty and ``batch`` while the online ring is (training
+    starts at tick 0 on loaded demonstrations, ``--load_replay_buffer``'s ``start_training = 0``)."""
+    f = float(demo_fraction)
+    if not 0.0 <= f <= 1.0:
+        raise ValueError(f"demo_fraction must be in [0, 1], got {demo_fraction!r}")
+    if demo_size == 0 and online_size == 0:
+        raise ValueError("MixedReplay: both rings are empty")
+    if demo_size == 0:
+        return 0
+    if online_size == 0:
+        return batch
+    return min(batch, int(math.floor(batch * f + 0.5)))
