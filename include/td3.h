@@ -50,6 +50,9 @@
  *                        demonstration replay (DDPGfD / RLPD symmetric sampling; the online half of
  *                        experience_injection.py + main.py --load_replay_buffer): every batch draws a fixed
  *                        number of rows from a demonstration ring and the rest from the online ring
+ *   td3_set_bc_filter / td3_bc_filter_info / td3_bc_filter_keep
+ *                        the BC term on the demonstration rows of a mixed batch only, with a Q-filter (Nair et
+ *                        al. 2018; no counterpart in the reference): fine-tuning on top of demonstrations
  *   td3_set_grad_clip / td3_clip_info
  *                        torch.nn.utils.clip_grad_norm_ between backward() and step() (one line with the
  *                        reference's torch classes): global-norm clipping of either group's gradient, on device
@@ -738,7 +741,7 @@ int td3_bc_info(td3_handle* h, td3_bc_info_t* info);
  * inject_idx: host [batch], nullable; its first n_demo entries index `demo`, the rest `rb`, each checked
  *   against its ring's capacity.  inject_noise, stats (stats->idx: the drawn rows, each in its own ring),
  *   the host synchronisations they force, the counters, the training log (prioritized = 0), TD3+BC (its
- *   term covers every row of the batch) and gradient clipping are td3_train_step's.
+ *   term covers every row of the batch unless td3_set_bc_filter narrows it) and gradient clipping are td3_train_step's.
  * Ordering: the step is ordered after every add queued on either ring before it, and adds to either ring
  *   queued after it wait for its reads (one read section on `rb`, then `demo`).
  * Mixing step kinds: a mixed step after a prioritized one refills unit weights; a plain or prioritized
@@ -756,6 +759,66 @@ int td3_bc_info(td3_handle* h, td3_bc_info_t* info);
 int td3_train_step_mixed(td3_handle* h, rb_handle* rb, rb_handle* demo, int batch, int n_demo, void* stream,
                          const int64_t* inject_idx, const float* inject_noise, td3_step_stats* stats);
 int td3_debug_mixed_input(td3_handle* h, rb_handle* rb, rb_handle* demo, void* stream);  /* re-queue the last mixed step's input launch (measurement) */
+
+/* ------------------------------------------------------------------ BC on the demonstration rows, Q-filter */
+/* Which rows of the batch the TD3+BC term covers (Nair et al. 2018, "Overcoming Exploration in Reinforcement
+ * Learning with Demonstrations", §IV-B/C): the rule for fine-tuning on top of demonstrations, the workflow
+ * td3_train_step_mixed exists for.  td3_set_bc alone is the offline rule (every row of the batch is data to
+ * imitate); on a mixed batch that also pulls pi(s) toward the learner's own old, noise-perturbed actions in
+ * the online rows.  Two switches, each 0 or 1, both 0 being exactly the step of "TD3+BC" above.  A featured
+ * learner, one device, every norm, a step whose delayed policy update runs with alpha > 0; B, A, pi_r, a_r,
+ * g_r,o and lambda as in "TD3+BC" -- lambda = alpha / mean over ALL B rows of |Q1(s_r, pi_r)|, unchanged:
+ *   n_d    = the step's n_demo if demo_rows (td3_train_step_mixed: its n_demo argument; every other step
+ *            kind: B -- a step that draws from one ring has no online rows), else B
+ *   cand_r = r < n_d
+ *   keep_r = cand_r and (not q_filter or Q1sa_r > Q1pi_r)        strict >, a float32 compare: a NaN on
+ *            either side drops the row
+ *            Q1sa_r = Q1(s_r, a_r) as this step's critic phase computed it: the critic BEFORE this step's
+ *                     update, the value in the step's TD error (td3_step_stats.q1)
+ *            Q1pi_r = Q1(s_r, pi_r) as the actor phase computes it: the critic AFTER the update
+ *   dL/dpi_r,o = lambda g_r,o + keep_r c (pi_r,o - a_r,o),       c = (float)(2.0 / ((double)n_d * A))
+ *   bc_loss    = sum_{r<B} keep_r sum_o (pi_r,o - a_r,o)^2 / (n_d A)       (0 when n_d = 0)
+ *   kept       = sum_{r<B} keep_r
+ * The two Q values come from critics one Adam step apart, on purpose: Q1(s, a) of the updated critic would
+ * cost a second Q1 forward per actor step, and the filter asks which of two actions the critic rates
+ * higher, which one step of Adam rarely changes.  The term is normalised by the candidate count n_d, not
+ * by kept, also on purpose: it weakens as the filter drops rows and fades once the policy overtakes the
+ * demonstrator.  With n_d = 0 no row is a candidate, c is never used and the step is lambda-scaled TD3.
+ * With n_d = B, c is the constant of "TD3+BC" bit for bit, and with every row kept so is the step.
+ * Everything behind dL/dpi is the plain step's; the critic phase is untouched; importance weights of a
+ * prioritized step still touch only the critic.
+ *
+ * On the device: a third form of the actor_head_bwd row stage (csrc/bcf.hip, td3_stage_kernel names it
+ * td3::row_bcf_kernel); nothing else in the stage list changes.  Each row's wave decides keep_r itself and
+ * forms c in float64 from n_d, once; a row that is not kept writes 0 as its squared error and adds no BC
+ * term.  No reduction beyond lambda's, no atomics.  n_d is a 4-byte device word the step plan owns: with
+ * demo_rows on, every actor step of td3_train_step, td3_train_step_batch, td3_train_step_prioritized
+ * (each n_d = B; td3_profile_stages and td3_probe_kernel too) and td3_train_step_mixed (n_d = n_demo)
+ * queues a 4-byte write of it on the step's stream ahead of the step's body, outside every captured
+ * graph, so n_demo may change every step with no plan rebuild and no re-capture.  With demo_rows off
+ * nothing is queued: the word holds B from the plan's build.
+ *
+ * td3_set_bc_filter: stores the switches; while alpha > 0 a changed switch synchronises the learner and
+ *   rebuilds the step plan and its captured graphs (as td3_set_bc does).  With alpha == 0 they wait for
+ *   td3_set_bc; with both 0 the learner is the one never touched: the same stage lists, kernels and bits.
+ *   Returns -1 with a message, before any GPU work, for (checked in this order): a switch that is not 0 or
+ *   1; a null handle; a particle handle; a handle in a td3_comm_init / td3_comm_init_local group.
+ * td3_bc_filter_info: synchronous like td3_bc_info.  `step` is total_it of the last actor step taken with
+ *   the filtered form in the current step plan, 0 if none (a plan rebuild forgets it), and then n_demo,
+ *   kept and bc_loss are 0.  n_demo is that step's n_d; kept and bc_loss are summed on the host from the
+ *   rows' keep flags and squared errors, in row order, in float64.  td3_bc_info.bc_loss reports the same
+ *   masked value on such a step.  Returns -1 for a null info, then a null handle.
+ * td3_bc_filter_keep: that step's keep_r as 0.0f / 1.0f, host keep[n], n = its batch size; synchronous;
+ *   -1 without such a step.  No existing struct changes. */
+typedef struct td3_bc_filter_info_t {
+  int demo_rows, q_filter;
+  int64_t step;
+  int64_t n_demo, kept;
+  double bc_loss;
+} td3_bc_filter_info_t;
+int td3_set_bc_filter(td3_handle* h, int demo_rows, int q_filter);
+int td3_bc_filter_info(td3_handle* h, td3_bc_filter_info_t* info);
+int td3_bc_filter_keep(td3_handle* h, float* keep, int n);
 
 /* ------------------------------------------------------------------ gradient clipping */
 /* torch.nn.utils.clip_grad_norm_ with its defaults (norm_type = 2, error_if_nonfinite = False) between a

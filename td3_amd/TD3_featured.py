@@ -205,9 +205,11 @@ class TD3(TD3_base):
 
     def __init__(self, obs_space, action_space, max_action=1, lr=1e-4, norm=None, CDQ=True,
                  device=None, seed=0, use_graph="auto", actor_arch=ACTOR_ARCH, q_arch=Q_ARCH,
-                 init="torch", bc_alpha=None, max_grad_norm=None, **kwargs):
+                 init="torch", bc_alpha=None, max_grad_norm=None, bc_rows="all", bc_q_filter=False, **kwargs):
         super().__init__(max_action=max_action, **kwargs)
         self._lib = _lib.load()
+        if bc_rows not in ("all", "demo"):
+            raise ValueError(f"bc_rows={bc_rows!r} is not supported ('all' or 'demo')")
         if norm not in (None, "layer", "weight_normalization"):
             raise ValueError(f"norm={norm!r} is not supported (None, 'layer' or 'weight_normalization')")
         if norm == "weight_normalization" and any(_clip_pair(max_grad_norm)):
@@ -255,6 +257,11 @@ class TD3(TD3_base):
             self.set_weights(a0, c0)
         # TD3+BC (Fujimoto & Gu 2021) for offline / demonstration-heavy buffers: the weight of the Q term
         # is bc_alpha / mean |Q|, next to an MSE between the policy's and the stored action (None / 0: off)
+        # which rows that MSE covers (Nair et al. 2018): "demo" keeps it to the demonstration rows of a
+        # MixedReplay batch, bc_q_filter to the rows whose stored action the critic still rates above pi(s)
+        self._bc_rows, self._bc_q_filter, self._last_batch = "all", False, 0
+        if bc_rows != "all" or bc_q_filter:
+            self._set_bc_filter(bc_rows, bc_q_filter)
         if bc_alpha:
             self.bc_alpha = bc_alpha
         # torch.nn.utils.clip_grad_norm_ ahead of each group's Adam step: a float, or (actor, critic)
@@ -333,6 +340,52 @@ class TD3(TD3_base):
         check(self._lib.td3_bc_info(self._h, C.byref(info)), "td3_bc_info")
         return {"enabled": bool(info.enabled), "alpha": info.alpha, "step": info.step, "lambda": getattr(info, "lambda"),
                 "q_abs_mean": info.q_abs_mean, "bc_loss": info.bc_loss}
+
+    def _set_bc_filter(self, rows, q_filter):
+        if rows not in ("all", "demo"):
+            raise ValueError(f"bc_rows={rows!r} is not supported ('all' or 'demo')")
+        check(self._lib.td3_set_bc_filter(self._h, 1 if rows == "demo" else 0, 1 if q_filter else 0),
+              "td3_set_bc_filter")
+        self._bc_rows, self._bc_q_filter = rows, bool(q_filter)
+
+    @property
+    def bc_rows(self):
+        """The rows of the batch the BC term covers: ``"all"`` (TD3+BC, the offline rule) or ``"demo"`` -- on a
+        ``MixedReplay`` step its ``n_demo`` demonstration rows only, every row on any other step (a step
+        that draws from one ring has no online rows).  Settable between steps (``td3_set_bc_filter``: with
+        ``bc_alpha`` set, a change synchronises the learner and rebuilds its step plan)."""
+        return self._bc_rows
+
+    @bc_rows.setter
+    def bc_rows(self, v):
+        self._set_bc_filter(v, self._bc_q_filter)
+
+    @property
+    def bc_q_filter(self):
+        """The Q-filter of Nair et al. 2018: a candidate row keeps its BC term only while
+        ``Q1(s, a_stored) > Q1(s, pi(s))``, so the term fades as the policy overtakes the demonstrator.
+        Settable between steps like ``bc_rows``."""
+        return self._bc_q_filter
+
+    @bc_q_filter.setter
+    def bc_q_filter(self, v):
+        self._set_bc_filter(self._bc_rows, v)
+
+    def bc_filter_info(self, keep=False):
+        """``td3_bc_filter_info`` as a dict: ``demo_rows``, ``q_filter``, ``step`` (``total_it`` of the last
+        actor step taken with a switch on, 0 if none), ``n_demo`` (its candidate rows), ``kept`` and the masked
+        ``bc_loss``; with ``keep=True`` and such a step also ``"keep"``, its rows' mask as a bool array.
+        Synchronous."""
+        info = _lib.td3_bc_filter_info_t()
+        check(self._lib.td3_bc_filter_info(self._h, C.byref(info)), "td3_bc_filter_info")
+        out = {"demo_rows": bool(info.demo_rows), "q_filter": bool(info.q_filter), "step": info.step,
+               "n_demo": info.n_demo, "kept": info.kept, "bc_loss": info.bc_loss}
+        if keep and info.step:
+            # the plan's batch is the last train_step's: a new size rebuilds the plan (step = 0)
+            rows = np.empty(self._last_batch, np.float32)
+            check(self._lib.td3_bc_filter_keep(self._h, _lib.fptr(rows), rows.size), "td3_bc_filter_keep")
+            out["keep"] = rows != 0
+        return out
 
     @property
     def max_grad_norm(self):
@@ -519,10 +572,12 @@ class TD3(TD3_base):
         the device; ``u`` (``[batch_size]`` mass fractions) replaces that draw and the stats gain
         ``"weight"`` and ``"td_abs"``.  With ``bc_alpha`` set, the stats of an actor step gain
         ``"bc_lambda"``, ``"bc_q_abs_mean"``, ``"bc_loss"`` and ``"bc_actor_loss"`` (= -lambda mean Q +
-        bc_loss; ``"actor_loss"`` keeps its meaning, -mean Q).  With ``max_grad_norm`` set, the stats gain
+        bc_loss; ``"actor_loss"`` keeps its meaning, -mean Q), and with ``bc_rows="demo"`` or ``bc_q_filter`` also
+        ``"bc_n_demo"`` and ``"bc_kept"`` (``bc_loss`` is then the masked term's).  With ``max_grad_norm`` set, the stats gain
         ``"critic_grad_norm"`` and ``"critic_clip_coef"``, and on actor steps ``"actor_grad_norm"`` and
         ``"actor_clip_coef"`` (each for a group that clips)."""
         B = int(batch_size)
+        self._last_batch = B
         st = None
         keep = []
         if stats:
@@ -603,6 +658,9 @@ class TD3(TD3_base):
                 bi = self.bc_info()
                 out["bc_lambda"], out["bc_q_abs_mean"], out["bc_loss"] = bi["lambda"], bi["q_abs_mean"], bi["bc_loss"]
                 out["bc_actor_loss"] = bi["lambda"] * st.actor_loss + bi["bc_loss"]
+                if self._bc_rows == "demo" or self._bc_q_filter:
+                    fi = self.bc_filter_info()
+                    out["bc_n_demo"], out["bc_kept"] = fi["n_demo"], fi["kept"]
         self._clip_stats(out, bool(st.actor_step))
         if prioritized:
             out["weight"], out["td_abs"] = weight, td_abs

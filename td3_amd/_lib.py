@@ -107,6 +107,11 @@ class td3_bc_info_t(C.Structure):
                 ("q_abs_mean", C.c_double), ("bc_loss", C.c_double)]
 
 
+class td3_bc_filter_info_t(C.Structure):
+    _fields_ = [("demo_rows", C.c_int), ("q_filter", C.c_int), ("step", C.c_int64), ("n_demo", C.c_int64),
+                ("kept", C.c_int64), ("bc_loss", C.c_double)]
+
+
 class td3_clip_info_t(C.Structure):
     _fields_ = [("enabled", C.c_int * 2), ("max_norm", C.c_double * 2), ("step", C.c_int64 * 2),
                 ("grad_norm", C.c_double * 2), ("coef", C.c_double * 2)]
@@ -197,6 +202,9 @@ SIGNATURES = {
     "td3_log_set": (C.c_int, [_P, C.POINTER(td3_log_entry), C.c_int64, C.c_int64]),
     "td3_set_bc": (C.c_int, [_P, C.c_double]),
     "td3_bc_info": (C.c_int, [_P, C.POINTER(td3_bc_info_t)]),
+    "td3_set_bc_filter": (C.c_int, [_P, C.c_int, C.c_int]),
+    "td3_bc_filter_info": (C.c_int, [_P, C.POINTER(td3_bc_filter_info_t)]),
+    "td3_bc_filter_keep": (C.c_int, [_P, _F, C.c_int]),
     "td3_set_grad_clip": (C.c_int, [_P, C.c_int, C.c_double]),
     "td3_clip_info": (C.c_int, [_P, C.POINTER(td3_clip_info_t)]),
     "td3_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),

@@ -22,6 +22,7 @@ int td3_profile_stages(td3_handle* h, rb_handle* rbh, int batch, int actor_phase
   hipStream_t s = h->stream;
   TD3_RC(ensure_w4(h, s));
   TD3_RC(ensure_unit_weights(h, s));
+  TD3_RC(queue_bc_rows(h, actor_phase ? 1 : 0, batch, s));   // a profiled step draws from one ring: n_d = B
   TD3_RC(ring_begin_read(r, s));
   TD3_HIP(hipEventRecord(ev[0], s));
   if (!fused) TD3_RC(input_from_ring(h, r, P, false, s));

@@ -53,6 +53,8 @@ enum RowKind : int {
   kRowTargetLoss = 8,    // target heads -> y (:140-142), g_j = 2/B (Q_j - y) (:148), squared errors
   kRowLnBwd = 9,         // dZ = relu'(LN_bwd(dU)) of full rows (layer 0, no GEMM follows)
   kRowActorHeadBwdBc = 10,   // kRowActorHeadBwd of the TD3+BC actor loss: dL/dpi = lambda dQ1/da + 2/(B A) (pi - a)
+  kRowActorHeadBwdBcF = 11,  // the same with the BC term on the kept rows only (td3_set_bc_filter): rows r < n_d,
+                             // and with the Q-filter those with Q1(s, a) > Q1(s, pi); 2/(n_d A) in place of 2/(B A)
 };
 
 // ------------------------------------------------------------------ operand slots
@@ -236,6 +238,24 @@ enum : int {
 };
 }  // namespace actor_head_bwd_bc
 TD3_SLOTS_FIT(actor_head_bwd_bc);
+
+// kRowActorHeadBwdBcF (row_actor_head_bwd<.., BC = kBcFiltered>): kRowActorHeadBwdBc's operands (kBcScale is
+// not read: the wave forms 2/(n_d A) from the kNDemo word), then those of the row mask (td3_set_bc_filter)
+namespace actor_head_bwd_bcf {
+using namespace actor_head_bwd_bc;
+enum : int {
+  kQ1sa = actor_head_bwd_bc::kNumPtr,   // Q1(s, a) of the rows [Bp] (the critic phase's kRowUnitLoss wrote them)
+  kNDemo,        // one int32 word the plan owns: n_d, the candidate rows [0, n_d) of this step
+  kKeep,         // out: 1.0f for a row whose BC term is kept, 0.0f for every other row (pad rows too) [Bp]
+  kNumPtr
+};
+enum : int {
+  kQFilter = actor_head_bwd_bc::kNumInt,   // 1: keep a candidate row only while Q1(s, a) > Q1(s, pi)
+  kNumInt
+};
+enum : int { kNumFlt = actor_head_bwd_bc::kNumFlt };
+}  // namespace actor_head_bwd_bcf
+TD3_SLOTS_FIT(actor_head_bwd_bcf);
 
 // kRowActorHeadBwdP (row_actor_head_bwd_p): dQ1/da through lnorm1 of the Q1 input
 namespace actor_head_bwd_p {
@@ -628,6 +648,8 @@ int launch_rows2(int kind1, int kind2, int n1, const GemmTable& t, int Bp, hipSt
 int launch_heads(const HeadArgs& a, int nprob, hipStream_t s);
 // kRowActorHeadBwdBc (bc.hip), called by launch_rows with the table's wide problems marked and the stage's bytes
 int launch_rows_bc(const GemmTable& d, int lds, int Bp, hipStream_t s);
+// kRowActorHeadBwdBcF (bcf.hip), called the same way
+int launch_rows_bcf(const GemmTable& d, int lds, int Bp, hipStream_t s);
 // Dynamic LDS bytes of the calling thread's last launch_rows / launch_rows2 (the wide-head stage;
 // 0: every head was requested block by block; -1: no row launch yet): td3_debug_row_lds
 int last_row_lds();

@@ -200,7 +200,8 @@ static int wide_head_bytes(int kind, const GemmProb& p) {
     const int ad = p.exi[policy_head::kAd], ldw4 = p.exi[policy_head::kLdw4];
     if (ad <= kHeadRegs || ldw4 % 4 || !al16(p.ex[policy_head::kW4])) return 0;
     n = (size_t)ad * ldw4;
-  } else if (kind == kRowActorHeadBwd || kind == kRowActorHeadBwdBc) {   // (the BC kind keeps the plain kind's slots)
+  } else if (kind == kRowActorHeadBwd || kind == kRowActorHeadBwdBc ||
+             kind == kRowActorHeadBwdBcF) {   // (the BC kinds keep the plain kind's slots)
     namespace ab = actor_head_bwd;
     const int ad = p.exi[ab::kAd], ldw4 = p.exi[ab::kLdw4], ld1 = p.exi[ab::kLdW1T];
     if (ad <= kHeadRegs || !p.ex[ab::kW1T] || ld1 % 4 || ldw4 % 4 || !al16(p.ex[ab::kW1T]) || !al16(p.ex[ab::kW4]))
@@ -245,6 +246,8 @@ static int launch_rows_t(int kind, const GemmTable& d0, int Bp, hipStream_t s) {
       break;
     case kRowActorHeadBwdBc:   // its kernels live in bc.hip, a code object of their own
       return launch_rows_bc(d, lds, Bp, s);
+    case kRowActorHeadBwdBcF:  // and these in bcf.hip
+      return launch_rows_bcf(d, lds, Bp, s);
     case kRowCriticLossP:
       hipLaunchKernelGGL((row_kernel<kRowCriticLossP, NORM>), grid, dim3(64 * kRowWaves), 0, s, Bp, d);
       break;

@@ -164,6 +164,12 @@ struct Plan {
   // actor_head_bwd stage
   float *bc_se = nullptr, *bc_lam = nullptr;
   bool bc = false;
+  // The filtered BC term (td3_set_bc_filter; null / false unless bc and a switch is on): the rows' 0/1 mask
+  // [Bp] of the last actor step, and the int32 word its actor_head_bwd stage reads n_d from -- B from the
+  // plan's build on, rewritten ahead of every actor step's body while demo_rows is on (queue_bc_rows)
+  float* bcf_keep = nullptr;
+  int* bcf_nd = nullptr;
+  bool bcf = false;
   // particles: each critic's rows' sum over the Q outputs of |Q_j - y| (critic_loss_p::kTd), [J][Bp];
   // the prioritized step combines them into per_td (per_td_combine_kernel)
   float* per_tdj = nullptr;
@@ -409,6 +415,10 @@ struct td3_handle {
   // the current plan (0: none; the plan holds that step's lambda and row errors)
   double bc_alpha = 0.0;
   int64_t bc_step = 0;
+  // The BC term's row mask (td3_set_bc_filter): the two switches, and n_d of the last actor step queued with
+  // the filtered form in the current plan (td3_bc_filter_info's n_demo; bc_step is that step's total_it)
+  int bc_demo_rows = 0, bc_q_filter = 0;
+  int bcf_n_demo = 0;
   // Gradient clipping (td3_set_grad_clip), index = group (0 actor, 1 critic): the threshold (0: off), its
   // device state (allocated by the first call that turns a group on), and total_it of the group's last
   // optimizer step taken with clipping in the current plan (clip_has: there is one to report)
@@ -503,6 +513,11 @@ int check_ring(const td3_handle* h, const Ring* r, RingUser what);
 inline void note_bc_step(td3_handle* h, int actor_phase) {
   if (actor_phase && h->plan && h->plan->bc) h->bc_step = h->total_it;
 }
+// The candidate rows [0, n_d) of a step about to be queued on s (td3_set_bc_filter): with demo_rows on, an
+// actor step writes n_d to the plan's word ahead of its body -- a direct operation on the step's stream,
+// outside every captured graph, so n_d may change from step to step.  With demo_rows off the word keeps the
+// B the plan's build wrote and nothing is queued.  n_d: the mixed step's n_demo; B for every other step.
+int queue_bc_rows(td3_handle* h, int actor_phase, int n_d, hipStream_t s);
 // ---- clip.hip
 // whether the group `which` steps (AdamArgs::which: 0 critic, 1 actor) clips its gradient
 inline bool clip_on(const td3_handle* h, int which) { return h->clip_max[which == 1 ? 0 : 1] > 0.0; }

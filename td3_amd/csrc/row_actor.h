@@ -1,7 +1,7 @@
-// The device code shared by kernels.hip and bc.hip: the row kernels' context, the wide-head LDS stage and
-// the actor-head backward row (plain: kRowActorHeadBwd, instantiated in kernels.hip; BC: kRowActorHeadBwdBc,
-// instantiated in bc.hip, whose kernels so form a code object of their own and leave that of kernels.hip
-// as it is without them).
+// The device code shared by kernels.hip, bc.hip and bcf.hip: the row kernels' context, the wide-head LDS
+// stage and the actor-head backward row (plain: kRowActorHeadBwd, instantiated in kernels.hip; BC:
+// kRowActorHeadBwdBc, instantiated in bc.hip; BC on the kept rows only: kRowActorHeadBwdBcF, instantiated in
+// bcf.hip -- the kernels of each form a code object of their own and leave the others' as they are).
 #pragma once
 #include "dev.h"
 #include "kernels.h"
@@ -121,10 +121,29 @@ __device__ __forceinline__ float bc_grad(float ga, float lam, float bcs, float m
   return lam * ga + bcs * d;
 }
 
+// The row mask of the filtered BC term (td3_set_bc_filter; operands actor_head_bwd_bcf): row r keeps its
+// term while r < n_d (the step's candidate rows: its demonstration rows, or all B) and, with the Q-filter
+// (Nair et al. 2018), Q1(s_r, a_r) > Q1(s_r, pi_r) -- a strict fp32 compare, so a NaN on either side drops
+// the row.  Each wave decides its own row and forms c = (float)(2.0 / ((double)n_d * A)) from the device
+// word once; a row that is not kept gets c = 0 (n_d = 0 never uses the quotient).  Lane 0 writes keep[row].
+__device__ __forceinline__ bool bcf_keep(const GemmProb& P, const RowCtx& c, int ad, float* bcs) {
+  namespace bf = actor_head_bwd_bcf;
+  asm volatile("" ::"s"(P.ex[bf::kQ1sa]), "s"(P.ex[bf::kNDemo]), "s"(P.ex[bf::kKeep]), "s"(P.exi[bf::kQFilter]));
+  const float qsa = gld(P.ex[bf::kQ1sa] + c.row), qpi = gld(P.ex[bf::kQv] + c.row);
+  const int nd = *(const GAS int*)P.ex[bf::kNDemo];
+  const bool keep = c.row < nd && c.row < P.B && (!P.exi[bf::kQFilter] || qsa > qpi);
+  *bcs = keep ? (float)(2.0 / ((double)nd * (double)ad)) : 0.f;
+  if (c.lane == 0) gst(P.ex[bf::kKeep] + c.row, keep ? 1.f : 0.f);
+  return keep;
+}
+
 // ---- dQ1/da through Q1's first layer, then the actor's head and LN3 backward -------------
 // (operands: actor_head_bwd, kernels.h; BC: the TD3+BC row kind kRowActorHeadBwdBc, operands
-// actor_head_bwd_bc -- the two extra terms of dL/dpi, the row's squared BC error, and lambda)
-template <bool NORM, int RW = 1, bool BC = false>
+// actor_head_bwd_bc -- the two extra terms of dL/dpi, the row's squared BC error, and lambda; kBcFiltered:
+// kRowActorHeadBwdBcF, the same arithmetic with the row's c from bcf_keep and 0 as the squared error of a
+// row that is not kept)
+constexpr int kBcOff = 0, kBcAll = 1, kBcFiltered = 2;
+template <bool NORM, int RW = 1, int BC = kBcOff>
 __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowCtx& c) {
   using namespace actor_head_bwd;
   namespace bc = actor_head_bwd_bc;
@@ -157,11 +176,13 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
   }
   const float tl = c.lane < ad ? gld(P.ex[kTanh] + ((size_t)c.row * 32 + c.lane)) : 0.f;
   float al = 0.f, lam = 0.f, bcs = 0.f, se = 0.f;   // BC: lane o's stored action a_o, lambda, 2/(B A), sum of (pi - a)^2
+  bool keep = true;                                 // kBcFiltered: the row keeps its BC term
   if constexpr (BC) {
     asm volatile("" ::"s"(P.ex[bc::kQv]), "s"(P.ex[bc::kAct]), "s"(P.ex[bc::kRowSe]), "s"(P.ex[bc::kLam]),
                  "s"(P.exi[bc::kLdAct]), "s"(P.exf[bc::kAlpha]), "s"(P.exf[bc::kBcScale]));
     if (c.lane < ad) al = gld(P.ex[bc::kAct] + ((size_t)c.row * P.exi[bc::kLdAct] + sd + c.lane));
-    bcs = P.exf[bc::kBcScale];
+    if constexpr (BC == kBcFiltered) keep = bcf_keep(P, c, ad, &bcs);
+    else bcs = P.exf[bc::kBcScale];
     float qabs;
     lam = bc_lambda(bc_qabs_sum(P.ex[bc::kQv], P.B, c.lane), P.B, P.exf[bc::kAlpha], &qabs);
     if (c.row == 0 && c.lane == 0) {
@@ -209,7 +230,7 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
         }
     }
     if constexpr (BC)
-      if (c.lane == 0) gst(P.ex[bc::kRowSe] + c.row, live ? se : 0.f);
+      if (c.lane == 0) gst(P.ex[bc::kRowSe] + c.row, live && keep ? se : 0.f);
     rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
     ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);        // dZ3 of the actor
     rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);
@@ -277,7 +298,7 @@ __device__ __forceinline__ void row_actor_head_bwd(const GemmProb& P, const RowC
       }
   }
   if constexpr (BC)
-    if (c.lane == 0) gst(P.ex[bc::kRowSe] + c.row, live ? se : 0.f);
+    if (c.lane == 0) gst(P.ex[bc::kRowSe] + c.row, live && keep ? se : 0.f);
   rv_store(P.ex[kDU3] + (size_t)c.row * ld3, ld3, c.lane, gu3[0]);
   ln_bwd_rows<1>(gu3, h3, g3, mn3, rs3, K3, c.lane, NORM);        // dZ3 of the actor
   rv_store(P.Aout + (size_t)c.row * P.ldao, P.ldao, c.lane, gu3[0]);

@@ -161,6 +161,7 @@ int push_row_stage(std::vector<Stage>& st, std::vector<GemmProb>& probs, int kin
   char kname[64];
   snprintf(kname, sizeof(kname), "td3::row_kernel<%d>", kind);
   if (kind == kRowActorHeadBwdBc) snprintf(kname, sizeof(kname), "td3::row_bc_kernel");
+  if (kind == kRowActorHeadBwdBcF) snprintf(kname, sizeof(kname), "td3::row_bcf_kernel");
   st.push_back({name, [=](hipStream_t s) { return launch_rows(kind, t, Bp, s); }, 0, kname});
   return 0;
 }

@@ -104,6 +104,7 @@ static int build_step(td3_handle* h, int B) {
   P->ld_sa = pad32(sd + ad);
   P->fuse_gather = 2 * sd + ad + 2 <= 128;
   P->bc = h->bc_alpha > 0.0;                  // TD3+BC (td3_set_bc): the BC form of actor_head_bwd
+  P->bcf = P->bc && (h->bc_demo_rows || h->bc_q_filter);   // its filtered form (td3_set_bc_filter)
   const NetL& an = h->actor.nets[0];
   const NetL& q1 = h->critic.nets[0];
   const NetL& q2 = h->critic.nets[1];
@@ -131,6 +132,10 @@ static int build_step(td3_handle* h, int B) {
       P->bc_se = S.take(Bp);
       P->bc_lam = S.take(4);
     }
+    if (P->bcf) {
+      P->bcf_keep = S.take(Bp);
+      P->bcf_nd = (int*)S.take(4);
+    }
     alloc_eval(S, an, Bp, P->X_S2A, P->ld_sa, false, norm, false, P->TA);
     alloc_eval(S, q1, Bp, P->X_SA, P->ld_sa, true, norm, true, P->Q[0]);
     alloc_eval(S, q2, Bp, P->X_SA, P->ld_sa, true, norm, true, P->Q[1]);
@@ -143,6 +148,7 @@ static int build_step(td3_handle* h, int B) {
   {
     const std::vector<float> ones((size_t)Bp, 1.0f);
     TD3_HIP(hipMemcpy(P->per_w, ones.data(), (size_t)Bp * sizeof(float), hipMemcpyHostToDevice));
+    if (P->bcf) TD3_HIP(hipMemcpy(P->bcf_nd, &B, sizeof(int), hipMemcpyHostToDevice));   // n_d = B until a step says otherwise
   }
   const StageCtx cx{h, P->tables, Bp, B};
 
@@ -316,8 +322,18 @@ static int build_step(td3_handle* h, int B) {
           p.exf[bc::kAlpha] = (float)h->bc_alpha;
           p.exf[bc::kBcScale] = (float)(2.0 / ((double)B * ad));
         }
+        if (P->bcf) {
+          // the row mask: Q1(s, a) as the critic phase's heads stage left it (the critic before this step's
+          // update, td3_step_stats.q1) against kQv, Q1(s, pi) of the updated critic; n_d from the plan's word
+          namespace bf = actor_head_bwd_bcf;
+          p.ex[bf::kQ1sa] = P->Q[0].Qv;
+          p.ex[bf::kNDemo] = reinterpret_cast<float*>(P->bcf_nd);
+          p.ex[bf::kKeep] = P->bcf_keep;
+          p.exi[bf::kQFilter] = h->bc_q_filter;
+        }
         std::vector<GemmProb> v = {p};
-        TD3_RC(push_row_stage(st, v, P->bc ? kRowActorHeadBwdBc : kRowActorHeadBwd, Bp, "actor_head_bwd"));
+        const int kind = P->bcf ? kRowActorHeadBwdBcF : P->bc ? kRowActorHeadBwdBc : kRowActorHeadBwd;
+        TD3_RC(push_row_stage(st, v, kind, Bp, "actor_head_bwd"));
       }
       std::vector<BwdItem> ab = {{&an, Pa, &P->A, true}};
       BwdOpts abo;
@@ -901,6 +917,15 @@ static int run_body(td3_handle* h, int actor_phase, int inj, hipStream_t s, Ring
   return 0;
 }
 
+int queue_bc_rows(td3_handle* h, int actor_phase, int n_d, hipStream_t s) {
+  const Plan* P = h->plan.get();
+  if (!actor_phase || !P || !P->bcf) return 0;
+  if (!h->bc_demo_rows) n_d = P->B;
+  else TD3_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P->bcf_nd), n_d, 1, s));
+  h->bcf_n_demo = n_d;
+  return 0;
+}
+
 int build_plan(td3_handle* h, int B) {
   const bool was_sharded = h->dp_sharded && h->nranks > 1;
   h->bc_step = 0;                             // the last BC step's lambda / row errors go with the plan
@@ -1052,6 +1077,7 @@ int td3_train_step(td3_handle* h, rb_handle* rbh, int batch, void* stream, const
   if (inject_noise)
     TD3_HIP(hipMemcpyAsync(P->noise, inject_noise, (size_t)batch * h->ad * 4, hipMemcpyHostToDevice, s));
   const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
+  TD3_RC(queue_bc_rows(h, actor_phase, batch, s));
   if (inject_idx) {
     TD3_RC(input_from_ring(h, r, P, true, s));
     TD3_RC(run_body(h, actor_phase, inject_noise ? 1 : 0, s, nullptr));
@@ -1084,6 +1110,7 @@ static int prioritized_step(td3_handle* h, rb_handle* rbh, int batch, double bet
   const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
   P->per_w_dirty = true;
   P->per_ring_gen = r->gen;
+  TD3_RC(queue_bc_rows(h, actor_phase, batch, s));
   TD3_RC(ring_draw_prioritized(r, batch, beta, inject_u ? P->per_u : nullptr, P->d_inject_idx, P->d_idx, P->per_w, s));
   TD3_RC(input_from_ring(h, r, P, true, s));
   h->per_step = true;
@@ -1154,6 +1181,7 @@ int td3_train_step_mixed(td3_handle* h, rb_handle* rbh, rb_handle* demoh, int ba
   if (inject_noise)
     TD3_HIP(hipMemcpyAsync(P->noise, inject_noise, (size_t)batch * h->ad * 4, hipMemcpyHostToDevice, s));
   const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
+  TD3_RC(queue_bc_rows(h, actor_phase, n_demo, s));
   TD3_RC(input_from_rings(h, r, d, P, n_demo, inject_idx ? P->d_inject_idx : nullptr, s));
   TD3_RC(run_body(h, actor_phase, inject_noise ? 1 : 0, s, nullptr));
   TD3_RC(ring_end_read(r, s));                   // later adds to either ring wait for this step's reads
@@ -1220,6 +1248,7 @@ int td3_train_step_batch(td3_handle* h, const float* state, const float* action,
   if (inject_noise)
     TD3_HIP(hipMemcpyAsync(P->noise, inject_noise, (size_t)batch * h->ad * 4, hipMemcpyHostToDevice, s));
   const int actor_phase = ((h->total_it + 1) % h->cfg.policy_freq) == 0;
+  TD3_RC(queue_bc_rows(h, actor_phase, batch, s));
   TD3_RC(input_from_batch(h, P, state, action, next_state, reward, not_done, s));
   TD3_RC(run_body(h, actor_phase, inject_noise ? 1 : 0, s, nullptr));
   if (inject_noise) TD3_HIP(hipStreamSynchronize(s));

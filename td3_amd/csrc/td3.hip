@@ -487,7 +487,70 @@ int td3_bc_info(td3_handle* h, td3_bc_info_t* info) {
   info->step = h->bc_step;
   info->lambda = lam[0];
   info->q_abs_mean = lam[1];
-  info->bc_loss = sum / ((double)P->B * h->ad);
+  // (a filtered step: the rows that are not kept wrote 0, and the term is normalised by its n_d candidates)
+  const double n_d = P->bcf ? (double)h->bcf_n_demo : (double)P->B;
+  info->bc_loss = n_d > 0 ? sum / (n_d * h->ad) : 0.0;
+  return 0;
+}
+
+// The BC term's row mask (include/td3.h, "BC on the demonstration rows, Q-filter"): the switches pick the
+// row kind of the actor_head_bwd stage (build_step), so a change while BC is on rebuilds the plan.
+int td3_set_bc_filter(td3_handle* h, int demo_rows, int q_filter) {
+  TD3_ARG((demo_rows == 0 || demo_rows == 1) && (q_filter == 0 || q_filter == 1), "demo_rows and q_filter must be 0 or 1");
+  TD3_ARG(h != nullptr, "null handle");
+  TD3_ARG(!h->particles, "td3_set_bc_filter on a particle learner (the particle learner has no BC step yet)");
+  TD3_ARG(!h->comm && !h->local,
+          "td3_set_bc_filter on a data-parallel handle (comm group attached): BC is not supported there");
+  if (h->bc_demo_rows == demo_rows && h->bc_q_filter == q_filter) return 0;
+  if (!(h->bc_alpha > 0.0)) {                   // no plan reads them while BC is off
+    h->bc_demo_rows = demo_rows;
+    h->bc_q_filter = q_filter;
+    return 0;
+  }
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_HIP(hipStreamSynchronize(h->stream));
+  h->bc_demo_rows = demo_rows;
+  h->bc_q_filter = q_filter;
+  h->bc_step = 0;
+  if (h->plan) TD3_RC(build_plan(h, h->plan->B));
+  return 0;
+}
+
+int td3_bc_filter_info(td3_handle* h, td3_bc_filter_info_t* info) {
+  TD3_ARG(info != nullptr, "null info");
+  TD3_ARG(h != nullptr, "null handle");
+  *info = td3_bc_filter_info_t{};
+  info->demo_rows = h->bc_demo_rows;
+  info->q_filter = h->bc_q_filter;
+  const Plan* P = h->plan.get();
+  if (!h->bc_step || !P || !P->bcf) return 0;
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_HIP(hipDeviceSynchronize());              // the last step may sit on a caller's stream
+  std::vector<float> se((size_t)P->B), keep((size_t)P->B);
+  TD3_HIP(hipMemcpy(se.data(), P->bc_se, se.size() * 4, hipMemcpyDeviceToHost));
+  TD3_HIP(hipMemcpy(keep.data(), P->bcf_keep, keep.size() * 4, hipMemcpyDeviceToHost));
+  double sum = 0;
+  int64_t kept = 0;
+  for (int r = 0; r < P->B; ++r) {
+    sum += (double)se[r];
+    kept += keep[r] != 0.f;
+  }
+  info->step = h->bc_step;
+  info->n_demo = h->bcf_n_demo;
+  info->kept = kept;
+  info->bc_loss = h->bcf_n_demo > 0 ? sum / ((double)h->bcf_n_demo * h->ad) : 0.0;
+  return 0;
+}
+
+int td3_bc_filter_keep(td3_handle* h, float* keep, int n) {
+  TD3_ARG(keep != nullptr, "null keep");
+  TD3_ARG(h != nullptr, "null handle");
+  const Plan* P = h->plan.get();
+  TD3_ARG(h->bc_step && P && P->bcf, "no filtered BC step to report in the current step plan");
+  TD3_ARG(n == P->B, "n must be the batch size of that step");
+  TD3_HIP(hipSetDevice(h->cfg.device));
+  TD3_HIP(hipDeviceSynchronize());
+  TD3_HIP(hipMemcpy(keep, P->bcf_keep, (size_t)n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
