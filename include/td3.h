@@ -39,6 +39,9 @@
  *                        rollout statistics of a GPU-resident vector environment (no counterpart in the
  *                        reference): running observation / reward normalisation and the episode log,
  *                        one launch per tick
+ *   rb_state_moments / rb_normalize_states / rb_norm_info
+ *                        dataset normalisation (TD3+BC's state normalisation; no counterpart in the reference):
+ *                        a loaded ring's state moments into an rs handle and the ring normalised in place
  *   td3_log_enable / td3_log_info / td3_log_read / td3_log_set
  *                        the training log (no counterpart in the reference): per-step losses and Q
  *                        statistics of either learner in a device ring, one opt-in launch per logged step
@@ -393,6 +396,50 @@ int rs_get_state(const rs_handle* h, rs_state* st);
 int rs_set_state(rs_handle* h, const rs_state* st);
 int rs_read_episodes(const rs_handle* h, int64_t first, int64_t n, rs_episode* out, int64_t* first_out,
                      int64_t* n_out);
+
+/* ------------------------------------------------------------------ dataset normalisation */
+/* TD3+BC's second ingredient (Fujimoto & Gu 2021) for a ring that was loaded, not collected: the moments of
+ * the ring's states into an rs_handle, and the ring normalised in place with them -- both on the device,
+ * nothing read back.  Online rows then come through rs_tick with update = 0 on the same moments and the
+ * same element expression, so a row normalised in the ring and a row normalised by a tick have the same bits.
+ * (TD3+BC's own code divides by std + 1e-3; here the denominator is sqrt(var + obs_eps), as in rs_tick.)
+ *
+ * rb_state_moments: the fp64 (count, mean[c], m2[c]) of field 0 of the ring (state; features on a particle
+ *   ring) over the valid rows [0, size), for every column rs's col_mask enables, into rs's OBSERVATION
+ *   moments.  merge = 0 replaces them (count = size); merge = 1 merges into what is there by rs_tick's own
+ *   Chan expressions (d = mb - mean, tot = count + size, mean += d * size / tot,
+ *   m2 += m2b + d * d * count * size / tot, count = tot).  Every count copy of rs is set.  The return
+ *   moments, the accumulators and the episode log of rs are not touched; a masked column's moments are not
+ *   written.  Asynchronous on `stream` (NULL: the ring's own), ordered as a ring READ; rs is the caller's
+ *   to order (queue its ticks on the same stream).  Two launches, no float atomics.  The order of every
+ *   addition is a function of (size, obs_dim) alone, so runs repeat bit for bit whatever the grid:
+ *     - the rows are cut into chunks of R = 1024 consecutive ring rows, chunk k = rows [1024 k, 1024 k + 1024),
+ *       and a chunk into micro-blocks of 8 rows (the last of either may be short);
+ *     - a micro-block of n rows: s = the sum in row order, mb = s / n, m2b = sum (x - mb)^2 in row order --
+ *       never sum x^2 - n mean^2;
+ *     - with W the power of two covering min(obs_dim - 256 b, 256) for the column's block b of 256 columns
+ *       and P = 256 / W, partial p of a chunk takes the micro-blocks m = p (mod P) in ascending m by Chan's
+ *       merge (the first as it is), and the P partials are combined by a halving tree (p takes p + s,
+ *       s = P/2, ..., 1);
+ *     - second launch: partial l of 64 takes the chunks l, l + 64, ... in ascending order, the 64 by the
+ *       same halving tree (l takes l + s, s = 32, ..., 1), then the replace or the merge above.
+ * rb_normalize_states: rewrites in place the state and next_state columns (features and next_features) of
+ *   the rows [0, size) by rs_tick step 2: out = (float) clip((x - mean) / sqrt(m2 / count + obs_eps),
+ *   +-obs_clip) in fp64, rounded once; a masked column, or count == 0, leaves x bit for bit.  Action, reward,
+ *   not_done, the pad, the particle blocks and the rows at or past size keep their bits.  One launch,
+ *   asynchronous on `stream` (NULL: the ring's own), ordered as a ring WRITE; it ends the n-step lane as every
+ *   write does, leaves the priorities alone, and the ring remembers normalized = 1: a second call is refused.
+ *   rb_write_records and rb_fill_synthetic clear the flag; adds leave it (they are the caller's normalised rows).
+ * rb_norm_info: normalized, the ring's state width, and the rows the normalising call rewrote (0 while
+ *   normalized = 0); no GPU work.
+ * Checked in this order, each failure returning -1 before any GPU work with a message naming the fault:
+ *   rb null; rs null; merge 0 or 1 (rb_state_moments only); rs's obs_dim equals the ring's state width
+ *   ("dims"); both on one device; the ring is not empty ("empty"); rb_normalize_states only: the ring is
+ *   not "already normalised".   rb_norm_info: info non-null; the handle. */
+typedef struct rb_norm_info_t { int normalized; int obs_dim; int64_t rows; } rb_norm_info_t;
+int rb_state_moments(rb_handle* rb, rs_handle* rs, int merge, void* stream);
+int rb_normalize_states(rb_handle* rb, const rs_handle* rs, void* stream);
+int rb_norm_info(const rb_handle* rb, rb_norm_info_t* info);
 
 /* ------------------------------------------------------------------ learner */
 /* struct_size:sizeof(td3_config) as the caller compiled it.  td3_default_config sets it and

@@ -93,6 +93,10 @@ class rs_state(C.Structure):
                 ("ep_return_sum", C.c_double)]
 
 
+class rb_norm_info_t(C.Structure):
+    _fields_ = [("normalized", C.c_int), ("obs_dim", C.c_int), ("rows", C.c_int64)]
+
+
 class td3_log_entry(C.Structure):
     _fields_ = [("step", C.c_int64), ("batch", C.c_int32), ("actor_step", C.c_int32), ("prioritized", C.c_int32),
                 ("nonfinite", C.c_int32), ("critic_loss", C.c_double), ("actor_loss", C.c_double),
@@ -157,6 +161,9 @@ SIGNATURES = {
     "rs_get_state": (C.c_int, [_P, C.POINTER(rs_state)]),
     "rs_set_state": (C.c_int, [_P, C.POINTER(rs_state)]),
     "rs_read_episodes": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(rs_episode), _I64, _I64]),
+    "rb_state_moments": (C.c_int, [_P, _P, C.c_int, _P]),
+    "rb_normalize_states": (C.c_int, [_P, _P, _P]),
+    "rb_norm_info": (C.c_int, [_P, C.POINTER(rb_norm_info_t)]),
     "rb_read_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
     "rb_write_records": (C.c_int, [_P, C.c_int64, C.c_int64, _F, C.c_int64, C.c_int64]),
     "rb_sync": (C.c_int, [_P]),

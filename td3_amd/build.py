@@ -18,7 +18,7 @@ OUT = os.path.join(HERE, "libtd3hip.so")
 SOURCES = ["csrc/replay.hip", "csrc/kernels.hip", "csrc/encoder.hip", "csrc/td3.hip",
            "csrc/stages.hip", "csrc/step.hip", "csrc/act.hip", "csrc/dp.hip", "csrc/debug.hip",
            "csrc/rollout.hip", "csrc/trainlog.hip", "csrc/bc.hip", "csrc/clip.hip",
-           "csrc/mixed.hip", "csrc/bcf.hip"]
+           "csrc/mixed.hip", "csrc/bcf.hip", "csrc/ringnorm.hip"]
 ARCH = os.environ.get("TD3_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared",
          "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-value",

@@ -89,12 +89,22 @@ struct Ring {
   int* ns_age[2] = {nullptr, nullptr};   // device [ns_age_rows]: ticks of this environment's episode still maturing
   int64_t ns_age_rows = 0;
   PriTree pri;
+  // Dataset normalisation (ringnorm.hip; include/td3.h "dataset normalisation"): set by
+  // rb_normalize_states, cleared by rb_write_records and rb_fill_synthetic, left by the adds.
+  int normalized = 0;
+  int64_t norm_rows = 0;           // the rows that call rewrote
+  double* nm_part = nullptr;       // device scratch of rb_state_moments: the chunk partials, grown on demand
+  size_t nm_cap = 0;               // its doubles
 };
 
 // Reader protocol (Ring::read_stream): ring_begin_read before enqueuing reads on s (orders them
 // after the writes and the earlier readers of other streams), ring_end_read after them.
 int ring_begin_read(Ring* r, hipStream_t s);
 int ring_end_read(Ring* r, hipStream_t s);
+// Writer protocol (Ring::write_stream): ring_begin_write before enqueuing writes of the records or d_size
+// on s (orders them after every read and every other-stream write queued so far), ring_end_write after.
+int ring_begin_write(Ring* r, hipStream_t s);
+int ring_end_write(Ring* r, hipStream_t s);
 // A stream that is about to be destroyed (synchronised by the caller) stops being a ring's
 // noted reader / writer.
 void ring_forget_stream(hipStream_t s);

@@ -725,13 +725,13 @@ int ring_end_read(Ring* r, hipStream_t s) {
 
 // Writes (records, d_size) on `stream` start after every read and every other-stream write queued
 // so far (Ring::read_stream / write_stream).
-static int ring_begin_write(Ring* r, hipStream_t stream) {
+int ring_begin_write(Ring* r, hipStream_t stream) {
   TD3_RC(order_after(stream, r->read_stream, r->reads_pending, r->read_ev, r->reads_seen_by));
   TD3_RC(order_after(stream, r->write_stream, r->writes_pending, r->write_ev, r->writes_seen_by));
   return 0;
 }
 
-static int ring_end_write(Ring* r, hipStream_t stream) {
+int ring_end_write(Ring* r, hipStream_t stream) {
   r->write_stream = stream;
   r->writes_pending = true;
   r->writes_seen_by = nullptr;
@@ -949,6 +949,7 @@ int rb_destroy(rb_handle* h) {
   (void)hipFree(r->d_idx);
   (void)hipFree(r->pri.base);
   (void)hipFree(r->pri.d_max);
+  (void)hipFree(r->nm_part);
   for (int* age : r->ns_age) (void)hipFree(age);
   for (int i = 0; i < 2; ++i) {
     if (r->stage_buf_ev[i]) (void)hipEventSynchronize(r->stage_buf_ev[i]);
@@ -1347,6 +1348,7 @@ int rb_fill_synthetic(rb_handle* h, int64_t n, float max_action, uint64_t seed, 
   TD3_HIP(hipSetDevice(r->device));
   hipStream_t s = stream ? (hipStream_t)stream : r->stream;
   if (n > r->cap) n = r->cap;
+  r->normalized = 0;                                 // raw rows again (include/td3.h "dataset normalisation")
   TD3_RC(ring_begin_write(r, s));
   if (n > 0) {
     dim3 grid((unsigned)((n + 3) / 4));
@@ -1547,6 +1549,7 @@ int rb_write_records(rb_handle* h, int64_t start, int64_t n, const float* in, in
   r->ptr = ptr;
   r->size = size;
   r->ns_nhist = 0;                                   // the n-step lane ends with any other write
+  r->normalized = 0;                                 // the caller's rows: raw until normalised again
   TD3_HIP(hipMemcpy(r->d_size, &r->size, sizeof(int64_t), hipMemcpyHostToDevice));
   if (r->pri.on) {                                   // the loaded rows are new rows: max_priority each
     TD3_RC(pri_reset(r, r->size, r->stream));

@@ -16,8 +16,7 @@
 //     prefix count over `ended`.
 // `count` is kept once per column workgroup (all copies equal) so that no workgroup reads a word another
 // one writes in the same launch.
-#include "common.h"
-#include "../../include/td3.h"
+#include "rollout.h"
 
 #include <cmath>
 #include <new>
@@ -64,16 +63,6 @@ __device__ __forceinline__ double tree_sum(double* part, double v, int tid, int 
   return part[c];
 }
 
-__device__ __forceinline__ double clipd(double y, double lim) { return y > lim ? lim : (y < -lim ? -lim : y); }
-
-// Chan's merge of a batch (n rows, mean mb, sum of squared deviations m2b) into running moments.
-__device__ __forceinline__ void chan_merge(double& count, double& mean, double& m2, double n, double mb, double m2b) {
-  const double delta = mb - mean, tot = count + n;
-  mean += delta * n / tot;
-  m2 += m2b + delta * delta * count * n / tot;
-  count = tot;
-}
-
 __device__ __forceinline__ void normalise_cols(const float* in, float* out, int rows, int D, int col, int p, int P,
                                                bool on, double mean, double den, double lim) {
   if (!on) {                                        // masked column, or no moments yet: bit for bit
@@ -84,7 +73,7 @@ __device__ __forceinline__ void normalise_cols(const float* in, float* out, int 
 #pragma unroll 4
   for (int r = p; r < rows; r += P) {
     const size_t k = (size_t)r * D + col;
-    out[k] = (float)clipd(((double)in[k] - mean) / den, lim);
+    out[k] = norm_elem(in[k], mean, den, lim);
   }
 }
 
@@ -123,7 +112,7 @@ __device__ void rs_columns(const RsArgs& a, double* part) {
   }
   if (!live) return;
   const bool norm = on && cnt > 0.0;
-  const double den = norm ? sqrt(m2 / cnt + a.obs_eps) : 1.0;
+  const double den = norm ? norm_den(m2, cnt, a.obs_eps) : 1.0;
   if (a.obs && a.obs_out) normalise_cols(a.obs, a.obs_out, rows, D, col, p, P, norm, mean, den, a.obs_clip);
   if (a.next_obs && a.next_obs_out)
     normalise_cols(a.next_obs, a.next_obs_out, rows, D, col, p, P, norm, mean, den, a.obs_clip);
@@ -222,22 +211,6 @@ __global__ __launch_bounds__(kRsThreads) void rs_tick_kernel(const RsArgs a) {
   else
     rs_rewards(a, part, wave_cnt);
 }
-
-struct Stats {
-  int device = 0, rows = 0, obs_dim = 0, log_cap = 0, ncol = 0, W = 0;
-  rs_config cfg{};
-  void* base = nullptr;            // one allocation; the pointers below point into it
-  double* count_blk = nullptr;
-  double* mean = nullptr;
-  double* m2 = nullptr;
-  double* rscal = nullptr;
-  int64_t* iscal = nullptr;
-  double* G = nullptr;
-  double* ep_return = nullptr;
-  int32_t* ep_len = nullptr;
-  rs_episode* log = nullptr;
-  uint8_t* mask = nullptr;
-};
 
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 

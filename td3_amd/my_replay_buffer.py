@@ -385,6 +385,51 @@ class _RingBuffer(object):
             return out, idx_out
         return out
 
+    # ------------------------------------------------------------------ dataset normalisation
+    def _call_on_torch_stream(self, name, *args):
+        """A ring call in the order of torch's current stream: on that stream itself, or -- torch's
+        default stream is the null stream, which the C call reads as "the ring's own" -- on the ring's
+        stream between two waits (``_torch_order``), so the statistics' ticks on torch's stream and this
+        call see each other's results either way."""
+        stream = _torch().cuda.current_stream(self.device).cuda_stream
+        if stream:
+            self._call(name, *args, stream)
+        else:
+            with self._torch_order():
+                self._call(name, *args, None)
+
+    def state_moments(self, stats=None, *, merge=False, gamma=0.99, obs_clip=10.0, eps=1e-8, col_mask=None):
+        """The moments of the stored states (``state``; ``state_features`` of a particle ring) over the
+        rows ``[0, size)`` into the observation moments of ``stats`` (``rb_state_moments``: on the device,
+        on torch's current stream, nothing read back) -- what TD3+BC normalises a dataset with.  Without
+        ``stats`` a ``RolloutStats(1, state width)`` is made on the ring's device from ``gamma`` /
+        ``obs_clip`` / ``eps`` / ``col_mask``.  ``merge`` adds the ring's rows to the moments ``stats``
+        already holds (Chan's merge) instead of replacing them.  Returns ``stats``: hand
+        ``stats.frozen_copy(n_envs)`` to ``NormalizedVecEnv(..., update=False)`` for the online rows."""
+        from .rollout_stats import RolloutStats
+        self.flush()
+        if stats is None:
+            stats = RolloutStats(1, self._dims()[0], gamma=gamma, obs_clip=obs_clip, eps=eps, col_mask=col_mask,
+                                 device=self._dev)
+        self._call_on_torch_stream("rb_state_moments", self._h, stats._h, 1 if merge else 0)
+        return stats
+
+    def normalize_states(self, stats):
+        """Normalise the stored states and next states of the rows ``[0, size)`` in place with the
+        moments of ``stats`` (``rb_normalize_states``: ``rs_tick``'s own element expression, so these rows
+        and the rows a ``NormalizedVecEnv`` on the same frozen moments stores agree bit for bit).  Once
+        per ring: ``normalized`` is then set, until ``load`` / ``fill_synthetic`` bring raw rows again."""
+        self.flush()
+        self._call_on_torch_stream("rb_normalize_states", self._h, stats._h)
+        if self._shadow is not None:
+            self._shadow.valid = False           # rows the host never saw: save() writes the ring
+
+    @property
+    def normalized(self):
+        info = _lib.rb_norm_info_t()
+        check(self._lib.rb_norm_info(self._h, info), "rb_norm_info")
+        return bool(info.normalized)
+
     # ------------------------------------------------------------------ priorities
     def enable_priorities(self, alpha=0.6, eps=1e-6):
         """Prioritized replay (Schaul et al. 2016): per-row priorities in a sum tree next to the ring
@@ -669,7 +714,10 @@ class MixedReplay(object):
     online ring's fill nor ends when a FIFO overwrites them.  ``TD3.train`` / ``train_step`` given a
     ``MixedReplay`` take the step on the device (``td3_train_step_mixed``: one input launch reads both
     rings); everything that adds rows forwards to ``online``, so ``DeviceTrainLoop`` / ``TrainLoop``
-    take one unchanged.  ``demo_fraction`` is a plain attribute in [0, 1]: anneal it between steps."""
+    take one unchanged.  ``demo_fraction`` is a plain attribute in [0, 1]: anneal it between steps.
+    State normalisation is the rings' own: ``stats = mix.demo.state_moments()``,
+    ``mix.demo.normalize_states(stats)``, and the online rows through
+    ``NormalizedVecEnv(env, stats.frozen_copy(env.n_envs), norm_reward=False, update=False)``."""
 
     prioritized = False
 

@@ -198,6 +198,24 @@ class RolloutStats:
         other.load_state_dict(self.state_dict(), moments_only=True)
         return other
 
+    def host_normalizer(self):
+        """``f(x) -> float32`` with the observation moments read once (synchronises now, never again):
+        ``rs_tick`` step 2 in numpy -- fp64, one rounding, masked columns and ``count == 0`` passed
+        through -- for host loops in ``main.py``'s style (``state = f(state)`` before ``select_action``
+        and ``add``) on a ring normalised with these moments."""
+        sd = self.state_dict()
+        count, mean, clip = float(sd["count"]), sd["mean"].copy(), self.obs_clip
+        on = self.col_mask != 0
+        den = np.sqrt(sd["m2"] / count + self.eps) if count > 0 else np.ones_like(mean)
+
+        def f(x):
+            x = np.asarray(x, np.float32)
+            if count == 0:
+                return x.copy()
+            y = np.clip((x.astype(np.float64) - mean) / den, -clip, clip).astype(np.float32)
+            return np.where(on, y, x)
+        return f
+
     # ------------------------------------------------------------------ the log
     def info(self):
         inf = _lib.rs_info_t()
